@@ -5,12 +5,17 @@ One "step" = one full learner step (policy forward -> V-trace + loss + analytic 
 policy backward -> [RCCL all-reduce] -> optimizer) over one (T, B) batch of synthetic
 trajectories already resident in HBM. value = T * B_per_gpu * N * K / max-over-ranks(time).
 
-  python bench.py [--gpus N --steps K --warmup W] [--arch atari|mlp]
+  python bench.py [--gpus N --steps K --warmup W] [--arch atari|mlp] [--dump-outputs DIR] [--full]
   N > 1 either form: `python bench.py --gpus N` starts the N ranks itself (a child
   `python -m torch.distributed.run --nproc-per-node N bench.py ...`, launched before anything
   touches the GPU; rank 0's line is relayed, the child's exit code returned), or
   `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` directly.
   --gpus N with fewer than N visible devices, or disagreeing with a launcher's WORLD_SIZE, exits 2.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+ms_per_step, the configuration). --dump-outputs DIR writes what the last timed step left a
+caller (the updated parameters, the gradient, the policy logits and values) as DIR/<name>.npy.
+Everything below runs only with --full, after the timed region and the dump.
 
 The roofline object is measured live: HIP events around every kernel launch of a few
 profiled steps (after the timed region) give each kernel's mean duration; ALGORITHMIC work
@@ -211,6 +216,12 @@ def main():
     ap.add_argument("--seq-len", type=int, default=100)
     ap.add_argument("--batch", type=int, default=4096, help="per-GPU batch (weak scaling)")
     ap.add_argument("--num-actions", type=int, default=18)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sustained loop, the profiled steps (per-kernel and "
+                         "step rooflines, phases), the V-trace replays, a stats step (final_loss, grad_norm), the "
+                         "data-parallel report and the CPU baseline; the options below apply to --full only")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--sustain-seconds", type=float, default=10.0,
                     help="after the timed loop, run the step this long more and report the sustained rate")
@@ -258,15 +269,13 @@ def main():
         import torch  # noqa: F401
     from freeimpala_amd import _abi
     _abi.lib()
-    import torch  # noqa: F401,F811
-    import torch.distributed as dist
-    if ws > 1:
+    if ws > 1:  # one rank needs no launcher: a plain 1-GPU run does not load torch at all
+        import torch  # noqa: F401,F811
+        import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=ws)
 
-    from freeimpala_amd.launch import (broadcast_bytes, data_parallel_fields, gather_objects, max_over_ranks,
-                                       shard_columns, timed_steps)
+    from freeimpala_amd.launch import broadcast_bytes, max_over_ranks, shard_columns, timed_steps
     from freeimpala_amd.learner import DeviceLearner
-    from freeimpala_amd.roofline import step_roofline
 
     T, B, A = args.seq_len, args.batch, args.num_actions
     # rehearsal knobs for a one-GPU box (never set by the driver): FI_BENCH_DEVICE pins every
@@ -294,6 +303,60 @@ def main():
         elapsed = max_over_ranks(elapsed)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = T * B * N * args.steps / elapsed
+    dtype = "bf16" if args.arch == "atari" else "fp32"
+
+    # ---- what the last timed step left a caller, before anything else steps the learner
+    if args.dump_outputs and rank == 0:
+        dump_outputs(L, args.dump_outputs)
+
+    result = {
+        "metric": METRIC, "value": round(value, 1), "unit": "env-steps/s", "n_gpus": N,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
+        "data": "synthetic (Philox4x32-10 on device, resident in HBM; random-init Glorot params)",
+        "config": {
+            "workload": ("config#3 Atari-shaped conv policy 84x84x4, bf16 MFMA GEMMs + fp32 V-trace"
+                         if args.arch == "atari" else
+                         "MLP policy 128-256-256 fp32 (config#2 network) at the metric's T/B"),
+            "T": T, "B_per_gpu": B, "A": A, "global_batch": B * N, "seq_len": T,
+            "parallelism": f"dp{N}", "optimizer": "adam", "policy": args.arch,
+        },
+    }
+    if args.full:
+        full_report(args, L, result, ws, rank, N, ms_per_step, value, own_ms_per_step, barrier)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    L.close()
+    if ws > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(L, out_dir, budget_bytes=60 * 2**20):
+    """The arrays a caller of the timed path holds after its last step, as out_dir/<name>.npy
+    (float32): the updated parameters, the gradient that updated them, and the policy's logits
+    and values over the batch. An array that would take the total over the budget is cut to a
+    fixed, seeded sample of its elements (sorted indices, the same from run to run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": L.get_params(), "grads": L.tensor("grads"),
+              "logits": L.tensor("logits"), "values": L.tensor("values")}
+    left = budget_bytes
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        a = np.ascontiguousarray(a, np.float32).ravel()
+        share = left // (len(arrays) - i)  # what the arrays still to come leave this one
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a[idx]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def full_report(args, L, result, ws, rank, N, ms_per_step, value, own_ms_per_step, barrier):
+    """--full: every measurement beside the headline figure, run after the timed region and the
+    output dump, added to `result` in place."""
+    from freeimpala_amd.launch import data_parallel_fields, gather_objects, max_over_ranks, timed_steps
+    from freeimpala_amd.roofline import step_roofline
+    T, B, A = args.seq_len, args.batch, args.num_actions
 
     # ---- sustained rate: the same step for --sustain-seconds more (untimed for `value`): the
     # power-limited clock's steady state beside the K-step burst, and GPU activity long enough
@@ -365,18 +428,7 @@ def main():
         return dict(common, bound="mfma", achieved=round(ach, 2), peak=MFMA_PEAK_TFLOPS[dtype],
                     unit="TFLOP/s", frac=round(ach / MFMA_PEAK_TFLOPS[dtype], 4))
 
-    result = {
-        "metric": METRIC, "value": round(value, 1), "unit": "env-steps/s", "n_gpus": N,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
-        "data": "synthetic (Philox4x32-10 on device, resident in HBM; random-init Glorot params)",
-        "config": {
-            "workload": ("config#3 Atari-shaped conv policy 84x84x4, bf16 MFMA GEMMs + fp32 V-trace"
-                         if args.arch == "atari" else
-                         "MLP policy 128-256-256 fp32 (config#2 network) at the metric's T/B"),
-            "T": T, "B_per_gpu": B, "A": A, "global_batch": B * N, "seq_len": T,
-            "parallelism": f"dp{N}", "optimizer": "adam", "policy": args.arch,
-        },
+    result.update({
         "sustained": sustained,
         "roofline": roof(dominant) if dominant else None,
         # V-trace scan: ~20 us, so per-launch event brackets inside the step carry the dispatch
@@ -407,7 +459,7 @@ def main():
         # RCCL's own view of the data-parallel communicator (ncclCommCount / ncclCommUserRank)
         "comm": L.comm_info(),
         "counters_build": counters_build,
-    }
+    })
     if dp is not None:
         result["data_parallel"] = dp
     if rank == 0 and N == 1 and not args.no_cpu_baseline:
@@ -428,11 +480,6 @@ def main():
             result["speedup_vs_cpu"] = round(value / result["cpu_baseline"]["value"], 1)
         except Exception as e:  # the baseline is reported, never blocks the GPU number
             result["cpu_baseline"] = {"error": repr(e)}
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    L.close()
-    if ws > 1:
-        dist.destroy_process_group()
 
 
 def load_counters(arch, tba):

@@ -13,7 +13,7 @@ for SET in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
   i=$((i + 1))
   rm -rf "$OUT/pmcsq_$i"
   timeout -s KILL 120 rocprofv3 --pmc $SET --output-format csv -d "$OUT/pmcsq_$i" -o run \
-      -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline \
+      -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline \
       > "$OUT/pmcsq_$i.log" 2>&1
   rc=$?
   [ $rc -ne 0 ] && { echo "pmc pass $i rc=$rc"; tail -5 "$OUT/pmcsq_$i.log"; exit $rc; }

@@ -19,6 +19,6 @@ cd "$ROOT"
 # the CPU step is silent for ~1-2 min: a heartbeat file under gpurun_out shows it is alive
 ( while sleep 45; do date +%T >> "$OUT/heartbeat_r04.txt"; done ) &
 HB=$!
-timeout -k 10 900 python bench.py --arch atari --cpu-full > "$OUT/bench_atari_cpufull_r04.json" 2> "$OUT/bench_atari_cpufull_r04.err"
+timeout -k 10 900 python bench.py --full --arch atari --cpu-full > "$OUT/bench_atari_cpufull_r04.json" 2> "$OUT/bench_atari_cpufull_r04.err"
 rc=$?; kill $HB; echo "bench cpu-full rc=$rc"; cat "$OUT/bench_atari_cpufull_r04.json"; [ $rc -ne 0 ] && { tail -5 "$OUT/bench_atari_cpufull_r04.err"; exit $rc; }
 exit 0

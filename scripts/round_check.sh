@@ -19,7 +19,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 "$OUT/pytest_gpu_$TAG.log"; [ $rc -ne 0 ] &
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$TAG.txt" 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke_$TAG.txt"; [ $rc -ne 0 ] && exit $rc
 for A in atari mlp; do
-  timeout -k 10 400 python bench.py --arch $A > "$OUT/bench_${A}_$TAG.json" 2> "$OUT/bench_${A}_$TAG.err"
+  timeout -k 10 400 python bench.py --full --arch $A > "$OUT/bench_${A}_$TAG.json" 2> "$OUT/bench_${A}_$TAG.err"
   rc=$?; echo "bench $A rc=$rc"; cat "$OUT/bench_${A}_$TAG.json"; [ $rc -ne 0 ] && { tail -5 "$OUT/bench_${A}_$TAG.err"; exit $rc; }
 done
 export TMPDIR=/tmp
@@ -27,7 +27,7 @@ cd /tmp
 for A in atari mlp; do
   rm -rf "$OUT/prof_${A}_$TAG"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${A}_$TAG" -o run \
-      -- python3 "$ROOT/bench.py" --arch $A --steps 5 --warmup 2 --sustain-seconds 0 --no-cpu-baseline > "$OUT/prof_${A}_$TAG.log" 2>&1
+      -- python3 "$ROOT/bench.py" --full --arch $A --steps 5 --warmup 2 --sustain-seconds 0 --no-cpu-baseline > "$OUT/prof_${A}_$TAG.log" 2>&1
   rc=$?; echo "rocprof $A rc=$rc"; [ $rc -ne 0 ] && exit $rc
 done
 exit 0

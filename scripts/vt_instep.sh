@@ -11,7 +11,7 @@ timeout -k 10 240 python scripts/vtrace_bench.py $L --variant 1 --sets 6 > gpuru
 timeout -k 10 240 python scripts/vtrace_bench.py $L --variant 1 --sets 1 > gpurun_out/vti_warm_$TAG.txt 2>&1 || exit $?
 cat gpurun_out/vti_cold_$TAG.txt gpurun_out/vti_warm_$TAG.txt
 for v in ${VT_LIBS:-plain munt allnt plain}; do
-  FI_LIB_OVERRIDE=build/ab/lib_vt_$v.so timeout -k 10 300 python bench.py --arch ${ARCH:-atari} --no-cpu-baseline \
+  FI_LIB_OVERRIDE=build/ab/lib_vt_$v.so timeout -k 10 300 python bench.py --full --arch ${ARCH:-atari} --no-cpu-baseline \
       > gpurun_out/vti_bench_${v}_$TAG.json 2> gpurun_out/vti_bench_${v}_$TAG.err || exit $?
   python -c "
 import json,sys

@@ -135,7 +135,7 @@ def test_bench_gpus2_spawns_two_ranks_on_the_gpu_box():
                                                                "TORCHELASTIC_RUN_ID")}
     env.update(FI_BENCH_DEVICE="0", FI_BENCH_NO_COMM="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--arch", "mlp",
-                        "--steps", "3", "--warmup", "1", "--profile-steps", "1", "--sustain-seconds", "0.5",
+                        "--steps", "3", "--warmup", "1", "--full", "--profile-steps", "1", "--sustain-seconds", "0.5",
                         "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -144,7 +144,13 @@ int main(int argc, char** argv) {
     int rc;
     if (rank == 0) {
         rc = run_learner(world, P, lc);
-        if (rc != 0) MPI_Abort(MPI_COMM_WORLD, rc);  // actors would wait for replies forever
+        if (rc != 0) {
+            // mpiexec tears its output forwarding down on an abort without draining it: let the
+            // message above reach the launcher first, or it is lost about every second time
+            std::cerr.flush();
+            std::this_thread::sleep_for(std::chrono::milliseconds(250));
+            MPI_Abort(MPI_COMM_WORLD, rc);  // actors would wait for replies forever
+        }
     } else {
         rc = run_actor(rank, P, lc);
     }
