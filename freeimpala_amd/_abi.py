@@ -20,6 +20,12 @@ PHASES = ["ingest", "forward", "vtrace", "backward", "allreduce", "optimizer"]
 RECORD_BYTES = 1024
 # record schema inside one 1 KiB ELEMENT
 REC_OBS, REC_MU, REC_ACT, REC_REW, REC_DISC, REC_FLAGS = 0, 512, 768, 772, 776, 780
+# the Atari record: 28 ELEMENTs per step, the 84x84x4 u8 frame first, then the same header
+ATARI_RECORD_ELEMENTS = 28
+ATARI_RECORD_BYTES = 28 * 1024
+ATARI_FRAME_BYTES = 84 * 84 * 4
+ATARI_REC_FRAME, ATARI_REC_MU, ATARI_REC_ACT, ATARI_REC_REW, ATARI_REC_DISC, ATARI_REC_FLAGS = \
+    0, 28224, 28480, 28484, 28488, 28492
 
 
 class VtraceHparams(C.Structure):
@@ -57,6 +63,7 @@ SIGNATURES = {
     "fi_learner_param_count": ([_P], C.c_size_t),
     "fi_learner_param_bytes": ([_P], C.c_size_t),
     "fi_learner_entry_bytes": ([_P], C.c_size_t),
+    "fi_learner_record_bytes": ([_P], C.c_size_t),
     "fi_learner_step": ([_P, C.POINTER(_P), C.c_size_t, C.c_size_t, C.POINTER(StepStats)], C.c_int),
     "fi_learner_step_async": ([_P, C.POINTER(_P), C.c_size_t, C.c_size_t], C.c_int),
     "fi_learner_wait": ([_P, C.POINTER(StepStats)], C.c_int),
@@ -92,6 +99,7 @@ SIGNATURES = {
                                     C.c_int),
     "fi_ingest_records": ([_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t] + [_P] * 6,
                           C.c_int),
+    "fi_ingest_atari_records": ([_P, C.c_int, C.c_int, C.c_int, C.c_size_t] + [_P] * 6, C.c_int),
     "fi_synth_trajectories": ([C.c_uint64] + [C.c_int] * 6 + [C.c_float] + [_P] * 7, C.c_int),
 }
 

@@ -83,5 +83,10 @@ int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int 
 // actions outside [0, A) are counted into *bad (nullable) and stored clamped
 int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_bytes, float* obs,
                   float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad = nullptr);
+// Atari records (FI_ATARI_RECORD_BYTES per step): frames (T+1, B, 84, 84, 4) u8 plus the same
+// header tensors; entry_bytes % 16 == 0, rec and frames 16-byte aligned
+int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
+                        float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
+                        int* bad = nullptr);
 
 }  // namespace fi

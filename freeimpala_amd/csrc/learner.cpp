@@ -343,8 +343,13 @@ extern "C" size_t fi_learner_param_bytes(const fi_learner* l) {
     if (!l) return 0;
     return l->nparams * (l->cfg.publish_dtype == FI_PUBLISH_BF16 ? 2 : 4);
 }
+// one step's record in a host entry: a 1 KiB ELEMENT (MLP), 28 of them (Atari: frame + header)
+static size_t record_bytes(const fi_learner* l) {
+    return l->cfg.arch == FI_ARCH_ATARI ? (size_t)FI_ATARI_RECORD_BYTES : (size_t)FI_RECORD_BYTES;
+}
+extern "C" size_t fi_learner_record_bytes(const fi_learner* l) { return l ? record_bytes(l) : 0; }
 extern "C" size_t fi_learner_entry_bytes(const fi_learner* l) {
-    return l ? (size_t)(l->T + 1) * FI_RECORD_BYTES : 0;
+    return l ? (size_t)(l->T + 1) * record_bytes(l) : 0;
 }
 extern "C" void* fi_learner_stream(fi_learner* l) { return l ? (void*)l->stream : nullptr; }
 extern "C" int fi_learner_sync(fi_learner* l) {
@@ -575,9 +580,18 @@ static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out) {
         FI_HIP_CHECK(hipStreamWaitEvent(l->stream, l->h2d_done[s], 0));
         {
             Tag t(l, "ingest");
-            FI_TRY(ingest_launch(l->rec_slot[s], l->T, l->B, l->A, l->D, l->rec_entry_bytes,
-                                 l->cfg.arch == FI_ARCH_MLP ? l->obs : nullptr, l->mu, l->act,
-                                 l->rew, l->disc, l->stream, l->bad));
+            if (l->cfg.arch == FI_ARCH_MLP)
+                FI_TRY(ingest_launch(l->rec_slot[s], l->T, l->B, l->A, l->D, l->rec_entry_bytes, l->obs,
+                                     l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
+            else
+                // frames (like mu / act / rew / disc) is rewritten in place: every kernel that
+                // read it in the previous step -- the forward and the backward's conv1 weight
+                // gradient -- was enqueued on this same stream, so stream order puts them before
+                // the ingest. The only other stream with work of the previous step, comm_stream,
+                // touches grads and the reject flag alone, and was joined before that step's
+                // optimizer (BucketAllReduce::join).
+                FI_TRY(ingest_atari_launch(l->rec_slot[s], l->T, l->B, l->A, l->rec_entry_bytes,
+                                           l->frames, l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
         }
         FI_HIP_CHECK(hipEventRecord(l->ingest_done[s], l->stream));
     }
@@ -692,10 +706,7 @@ static void parallel_copy(char* dst, const void* const* entries, size_t n, size_
 // H2D that last read it is done; submit_slot() enqueues its H2D on the copy stream (after the
 // ingest that last read the device slot) and makes it the batch the next run_step ingests.
 static int ensure_staging(fi_learner* l) {
-    FI_REQUIRE(l->cfg.arch == FI_ARCH_MLP,
-               "step: host trajectory records carry <=128-float observations (MLP); the Atari "
-               "config is device-synthetic (fi_learner_synth_batch + fi_learner_step_resident)");
-    const size_t need = (size_t)(l->T + 1) * FI_RECORD_BYTES;
+    const size_t need = (size_t)(l->T + 1) * record_bytes(l);
     const size_t bytes = (size_t)l->B * need;
     if (bytes <= l->rec_bytes) return FI_OK;
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
@@ -712,7 +723,13 @@ static int ensure_staging(fi_learner* l) {
     }
     l->rec_bytes = 0;
     for (int i = 0; i < 2; ++i) {
-        FI_HIP_CHECK(hipHostMalloc((void**)&l->pinned2[i], bytes, hipHostMallocDefault));
+        const hipError_t e = hipHostMalloc((void**)&l->pinned2[i], bytes, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            l->pinned2[i] = nullptr;
+            (void)hipGetLastError();
+            return fail(FI_ERR_OOM, "step: hipHostMalloc(" + std::to_string(bytes) + ") for staging buffer " +
+                                        std::to_string(i) + " of 2: " + hipGetErrorString(e));
+        }
         FI_TRY(dalloc(l, (void**)&l->rec_slot[i], bytes));
         if (!l->h2d_done[i]) FI_HIP_CHECK(hipEventCreateWithFlags(&l->h2d_done[i], hipEventDisableTiming));
         if (!l->ingest_done[i]) FI_HIP_CHECK(hipEventCreateWithFlags(&l->ingest_done[i], hipEventDisableTiming));
@@ -764,8 +781,9 @@ static int submit_slot(fi_learner* l) {
 static int stage_entries(fi_learner* l, const void* const* entries, size_t n_entries, size_t entry_bytes) {
     FI_REQUIRE(l && entries, "step: null argument");
     FI_REQUIRE(n_entries == (size_t)l->B, "step: n_entries must equal the configured batch");
-    const size_t need = (size_t)(l->T + 1) * FI_RECORD_BYTES;
-    FI_REQUIRE(entry_bytes >= need, "step: entry_bytes < (T+1)*1024");
+    const size_t need = (size_t)(l->T + 1) * record_bytes(l);
+    FI_REQUIRE(entry_bytes >= need, "step: entry_bytes " + std::to_string(entry_bytes) + " < " +
+                                        std::to_string(need) + " = (T+1)*" + std::to_string(record_bytes(l)));
     for (size_t i = 0; i < n_entries; ++i) FI_REQUIRE(entries[i], "step: null entry");
     FI_HIP_CHECK(hipSetDevice(l->dev));
     int s = 0;

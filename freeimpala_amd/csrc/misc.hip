@@ -1,8 +1,11 @@
 // misc.hip -- HBM-bound helper kernels of the learner step (gfx950):
 //   * synthetic trajectories (Philox4x32-10, bit-identical to the oracle's generator)
-//   * ingest: (B, S*1024) SharedBuffer entries -> time-major SoA tensors
+//   * ingest: (B, S*1024) SharedBuffer entries -> time-major SoA tensors (MLP records, and the
+//     Atari records with their 84x84x4 frames)
 //   * column sums / split-K slab reduction (deterministic, fixed order)
 //   * global gradient norm, Adam / SGD with global-norm clipping, fp32 -> bf16
+#include <algorithm>
+
 #include "fi_common.h"
 #include "kernels.h"
 
@@ -109,38 +112,77 @@ int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int 
 }
 
 // ---------------------------------------------------------------- ingest
-// Record schema (one 1 KiB ELEMENT per step, reference data_structures.h:35, agent.h:62):
+// MLP record schema (one 1 KiB ELEMENT per step, reference data_structures.h:35, agent.h:62):
 //   [0,512) float obs[<=128] | [512,768) float mu_logits[<=64] | 768 int32 action |
 //   772 float reward | 776 float discount | 780 uint32 flags | 784.. reserved.
-// An entry holds T+1 records (record T = bootstrap observation).
-constexpr int REC_OBS = 0, REC_MU = 512, REC_ACT = 768, REC_REW = 772, REC_DISC = 776;
+// Atari record schema (28 ELEMENTs = 28,672 B per step, FI_ATARI_RECORD_BYTES):
+//   [0,28224) u8 frame 84x84x4 NHWC | [28224,28480) float mu_logits[<=64] | 28480 int32 action |
+//   28484 float reward | 28488 float discount | 28492 uint32 flags | 28496.. reserved.
+// Both headers have the same shape: mu, then action / reward / discount at +256 / +260 / +264.
+// An entry holds T+1 records (record T = bootstrap observation; its header is ignored).
+constexpr int REC_OBS = 0, REC_MU = 512;
+constexpr int HDR_ACT = 256, HDR_REW = 260, HDR_DISC = 264;  // relative to the record's mu
+constexpr int kFrameBytes = 84 * 84 * 4;
+constexpr int kFramePieces = kFrameBytes / 16;  // 1,764 16-byte pieces
+constexpr int ATARI_REC_MU = kFrameBytes;
+static_assert(ATARI_REC_MU + HDR_DISC + 8 <= FI_ATARI_RECORD_BYTES, "Atari record header");
+static_assert(FI_ATARI_RECORD_BYTES == FI_ATARI_RECORD_ELEMENTS * FI_RECORD_BYTES, "Atari record size");
 
 __global__ void ingest_vec_kernel(const char* __restrict__ rec, int rows, int B, int W,
-                                  int rec_off, size_t entry_bytes, float* __restrict__ out) {
+                                  int rec_off, size_t rec_stride, size_t entry_bytes,
+                                  float* __restrict__ out) {
     const size_t n = (size_t)rows * B * W;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
          i += (size_t)gridDim.x * blockDim.x) {
         const size_t lrow = i / W;
         const int d = (int)(i - lrow * W);
         const int t = (int)(lrow / B), b = (int)(lrow - (size_t)t * B);
-        out[i] = *(const float*)(rec + (size_t)b * entry_bytes + (size_t)t * FI_RECORD_BYTES +
+        out[i] = *(const float*)(rec + (size_t)b * entry_bytes + (size_t)t * rec_stride +
                                  rec_off + d * 4);
     }
 }
 
 __global__ void ingest_scalar_kernel(const char* __restrict__ rec, int T, int B, int A,
-                                     size_t entry_bytes, int32_t* act, float* rew, float* disc,
-                                     int* bad) {
+                                     int mu_off, size_t rec_stride, size_t entry_bytes,
+                                     int32_t* act, float* rew, float* disc, int* bad) {
     const size_t n = (size_t)T * B;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
          i += (size_t)gridDim.x * blockDim.x) {
         const int t = (int)(i / B), b = (int)(i - (size_t)t * B);
-        const char* r = rec + (size_t)b * entry_bytes + (size_t)t * FI_RECORD_BYTES;
-        int32_t a = *(const int32_t*)(r + REC_ACT);
+        const char* r = rec + (size_t)b * entry_bytes + (size_t)t * rec_stride + mu_off;
+        int32_t a = *(const int32_t*)(r + HDR_ACT);
         if ((unsigned)a >= (unsigned)A && bad) atomicAdd(bad, 1);
         act[i] = a < 0 ? 0 : (a >= A ? A - 1 : a);
-        rew[i] = *(const float*)(r + REC_REW);
-        disc[i] = *(const float*)(r + REC_DISC);
+        rew[i] = *(const float*)(r + HDR_REW);
+        disc[i] = *(const float*)(r + HDR_DISC);
+    }
+}
+
+// Frames of the Atari records -> the time-major frames tensor (T+1, B, 84, 84, 4): a strided
+// de-interleave of whole 28,224-byte frames. A workgroup owns a frame and grid-strides over
+// frames, so the (t, b) index work is done once per frame on the scalar unit; its 256 lanes
+// move the frame's 1,764 16-byte pieces, 7 per lane, every load issued before the first store.
+constexpr int kIngestFullRounds = kFramePieces / 256;                  // 6 rounds of all 256 lanes
+constexpr int kIngestTailLanes = kFramePieces - 256 * kIngestFullRounds;  // + 228 lanes once more
+
+__global__ __launch_bounds__(256) void ingest_frames_kernel(const char* __restrict__ rec, int n_frames,
+                                                            int B, size_t entry_bytes,
+                                                            uint4* __restrict__ frames) {
+    const int lane = threadIdx.x & 255;  // the launch uses 256 lanes: every piece index below is in range
+    const bool tail = lane < kIngestTailLanes;
+    for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
+        const int t = f / B, b = f - t * B;
+        const uint4* __restrict__ src =
+            (const uint4*)(rec + (size_t)b * entry_bytes + (size_t)t * FI_ATARI_RECORD_BYTES) + lane;
+        uint4* __restrict__ dst = frames + (size_t)f * kFramePieces + lane;
+        uint4 v[kIngestFullRounds];
+        uint4 vt = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int k = 0; k < kIngestFullRounds; ++k) v[k] = src[k * 256];
+        if (tail) vt = src[kIngestFullRounds * 256];
+#pragma unroll
+        for (int k = 0; k < kIngestFullRounds; ++k) dst[k * 256] = v[k];
+        if (tail) dst[kIngestFullRounds * 256] = vt;
     }
 }
 
@@ -149,15 +191,43 @@ int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_byte
     FI_REQUIRE(rec && T >= 1 && B >= 1 && A >= 1 && A <= 64 && D <= 128, "ingest: bad shape");
     FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * FI_RECORD_BYTES, "ingest: entry too small");
     const char* r = (const char*)rec;
+    const size_t stride = FI_RECORD_BYTES;
     if (obs)
         hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)(T + 1) * B * D)), dim3(256), 0, s,
-                           r, T + 1, B, D, REC_OBS, entry_bytes, obs);
+                           r, T + 1, B, D, REC_OBS, stride, entry_bytes, obs);
     if (mu)
         hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T,
-                           B, A, REC_MU, entry_bytes, mu);
+                           B, A, REC_MU, stride, entry_bytes, mu);
     if (act && rew && disc)
         hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T,
-                           B, A, entry_bytes, act, rew, disc, bad);
+                           B, A, REC_MU, stride, entry_bytes, act, rew, disc, bad);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+// workgroups of the frame copy: 8 per CU on 256 CUs, the rest of the frames by grid stride
+constexpr int kIngestFramesMaxGrid = 2048;
+
+int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
+                        float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad) {
+    FI_REQUIRE(rec && frames && mu && act && rew && disc, "ingest_atari: null argument");
+    FI_REQUIRE(T >= 1 && B >= 1 && A >= 1 && A <= 64, "ingest_atari: bad shape");
+    FI_REQUIRE((size_t)(T + 1) * (size_t)B <= (size_t)0x7fffffff, "ingest_atari: too many frames");
+    FI_REQUIRE(entry_bytes % 16 == 0, "ingest_atari: entry_bytes must be a multiple of 16");
+    FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * FI_ATARI_RECORD_BYTES,
+               "ingest_atari: entry_bytes < " + std::to_string((size_t)(T + 1) * FI_ATARI_RECORD_BYTES) +
+                   " = (T+1)*28672");
+    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)frames % 16 == 0,
+               "ingest_atari: records and frames must be 16-byte aligned");
+    const char* r = (const char*)rec;
+    const size_t stride = FI_ATARI_RECORD_BYTES;
+    const int n_frames = (T + 1) * B;
+    hipLaunchKernelGGL(ingest_frames_kernel, dim3(std::min(n_frames, kIngestFramesMaxGrid)), dim3(256), 0, s,
+                       r, n_frames, B, entry_bytes, (uint4*)frames);
+    hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T, B, A,
+                       ATARI_REC_MU, stride, entry_bytes, mu);
+    hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T, B, A,
+                       ATARI_REC_MU, stride, entry_bytes, act, rew, disc, bad);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -435,4 +505,11 @@ extern "C" int fi_ingest_records(const void* rec, int T, int B, int A, int D, si
                                  void* stream) {
     return fi::ingest_launch(rec, T, B, A, D, entry_bytes, obs, mu, act, rew, disc,
                              (hipStream_t)stream);
+}
+
+extern "C" int fi_ingest_atari_records(const void* rec, int T, int B, int A, size_t entry_bytes,
+                                       uint8_t* frames, float* mu, int32_t* act, float* rew,
+                                       float* disc, void* stream) {
+    return fi::ingest_atari_launch(rec, T, B, A, entry_bytes, frames, mu, act, rew, disc,
+                                   (hipStream_t)stream);
 }

@@ -65,6 +65,11 @@ class DeviceLearner:
     def entry_bytes(self) -> int:
         return int(lib().fi_learner_entry_bytes(self._h))
 
+    @property
+    def record_bytes(self) -> int:
+        """Bytes of one step's record in a host entry: 1024 (MLP), 28672 (Atari)."""
+        return int(lib().fi_learner_record_bytes(self._h))
+
     # --- the step
     def step(self, batch: Sequence[bytes | bytearray | np.ndarray] | HostBatch,
              stats: bool = True) -> dict:
@@ -281,3 +286,59 @@ def pack_records(obs, mu, actions, rewards, discounts, entry_size=None) -> list[
         rec[:T, 776:780] = np.ascontiguousarray(discounts[:, b], np.float32).view(np.uint8).reshape(T, 4)
         out.append(e.tobytes())
     return out
+
+
+def pack_atari_records(frames, mu, actions, rewards, discounts, entry_size=None) -> list[bytes]:
+    """Build SharedBuffer entries of Atari records from time-major arrays (inverse of the Atari
+    ingest kernel). frames (T+1,B,84,84,4) uint8, mu (T,B,A), actions/rewards/discounts (T,B).
+    Returns B entries of entry_size*1024 bytes (entry_size in 1 KiB elements, default
+    28*(T+1)); record T carries the bootstrap frame only."""
+    frames = np.asarray(frames, np.uint8)
+    T1, B = frames.shape[:2]
+    T = T1 - 1
+    A = mu.shape[-1]
+    R, FB = _abi.ATARI_RECORD_BYTES, _abi.ATARI_FRAME_BYTES
+    S = entry_size or _abi.ATARI_RECORD_ELEMENTS * T1
+    if S * 1024 < T1 * R:
+        raise ValueError(f"entry_size {S} < {_abi.ATARI_RECORD_ELEMENTS * T1} = 28*(T+1)")
+    fr = frames.reshape(T1, B, FB)
+    out = []
+    for b in range(B):
+        e = np.zeros(S * 1024, np.uint8)
+        rec = e[:T1 * R].reshape(T1, R)
+        rec[:, :FB] = fr[:, b]
+        h = rec[:T]
+        h[:, _abi.ATARI_REC_MU:_abi.ATARI_REC_MU + 4 * A] = \
+            np.ascontiguousarray(mu[:, b, :], np.float32).view(np.uint8).reshape(T, 4 * A)
+        for off, a, dt in ((_abi.ATARI_REC_ACT, actions, np.int32), (_abi.ATARI_REC_REW, rewards, np.float32),
+                           (_abi.ATARI_REC_DISC, discounts, np.float32)):
+            h[:, off:off + 4] = np.ascontiguousarray(a[:, b], dt).view(np.uint8).reshape(T, 4)
+        out.append(e.tobytes())
+    return out
+
+
+def unpack_atari_records(batch_bytes, T, B, A):
+    """Inverse of pack_atari_records: B entries (a sequence of byte strings / uint8 arrays of
+    equal length, or one buffer holding them back to back) -> (frames (T+1,B,84,84,4) uint8,
+    mu (T,B,A) float32, actions (T,B) int32, rewards (T,B), discounts (T,B) float32)."""
+    if isinstance(batch_bytes, (bytes, bytearray, memoryview, np.ndarray)):
+        buf = np.frombuffer(batch_bytes, np.uint8) if not isinstance(batch_bytes, np.ndarray) \
+            else np.ascontiguousarray(batch_bytes).view(np.uint8).ravel()
+    else:
+        buf = np.concatenate([np.frombuffer(e, np.uint8) if not isinstance(e, np.ndarray)
+                              else np.ascontiguousarray(e).view(np.uint8).ravel() for e in batch_bytes])
+    R, FB = _abi.ATARI_RECORD_BYTES, _abi.ATARI_FRAME_BYTES
+    if buf.size % B or buf.size // B < (T + 1) * R:
+        raise ValueError(f"{buf.size} bytes do not hold {B} entries of >= {(T + 1) * R} bytes")
+    rec = buf.reshape(B, -1)[:, :(T + 1) * R].reshape(B, T + 1, R)
+    frames = np.ascontiguousarray(rec[:, :, :FB].transpose(1, 0, 2)).reshape(T + 1, B, 84, 84, 4)
+    h = rec[:, :T]
+
+    def field(off, n, dt):
+        return np.ascontiguousarray(h[:, :, off:off + 4 * n].transpose(1, 0, 2)).view(dt)
+
+    mu = field(_abi.ATARI_REC_MU, A, np.float32)
+    act = field(_abi.ATARI_REC_ACT, 1, np.int32)[..., 0]
+    rew = field(_abi.ATARI_REC_REW, 1, np.float32)[..., 0]
+    disc = field(_abi.ATARI_REC_DISC, 1, np.float32)[..., 0]
+    return frames, mu, np.ascontiguousarray(act), np.ascontiguousarray(rew), np.ascontiguousarray(disc)

@@ -27,6 +27,10 @@ extern "C" {
 
 #define FI_ABI_VERSION 1
 #define FI_RECORD_BYTES 1024 /* == ELEMENT_SIZE, reference data_structures.h:35 */
+/* One step of the Atari policy: an 84x84x4 u8 frame (28,224 B) and its header in 28 ELEMENTs
+ * (record schema: DESIGN.md section 3).                                                    */
+#define FI_ATARI_RECORD_ELEMENTS 28
+#define FI_ATARI_RECORD_BYTES 28672
 
 enum fi_status {
     FI_OK = 0,
@@ -93,12 +97,17 @@ int fi_abi_version(void);
 /* ---- sizes ------------------------------------------------------------------------ */
 size_t fi_learner_param_count(const fi_learner* l);  /* fp32 parameters              */
 size_t fi_learner_param_bytes(const fi_learner* l);  /* published blob (fp32|bf16)   */
-size_t fi_learner_entry_bytes(const fi_learner* l);  /* minimum (T+1)*1024 per entry */
+size_t fi_learner_record_bytes(const fi_learner* l); /* one step's record: 1024 (MLP),
+                                                        28672 (Atari)                */
+size_t fi_learner_entry_bytes(const fi_learner* l);  /* minimum per entry:
+                                                        (T+1) * fi_learner_record_bytes */
 
 /* ---- the learner step ---------------------------------------------------------------
  * fi_learner_step: Learner::step(player, batch) body. entries[i] points at one
- * SharedBuffer entry (host memory, borrowed for the call only; entry_bytes >= (T+1)*1024,
- * record schema in DESIGN.md section 3). n_entries must equal cfg.batch. The call stages
+ * SharedBuffer entry (host memory, borrowed for the call only; entry_bytes >=
+ * fi_learner_entry_bytes(): (T+1)*1024 for the MLP, (T+1)*28672 and a multiple of 16 for the
+ * Atari policy; record schemas in DESIGN.md section 3). n_entries must equal cfg.batch. Only
+ * the first fi_learner_entry_bytes() bytes of each entry are read. The call stages
  * the batch (pinned copy + async H2D), runs ingest -> policy fwd -> V-trace/loss -> bwd
  * -> [RCCL all-reduce] -> optimizer, and returns when the step has completed.
  * fi_learner_step_resident: same step on the batch already resident in HBM (filled by
@@ -125,7 +134,9 @@ int fi_learner_wait(fi_learner* l, fi_step_stats* out);
  * fi_learner_step_staged (returns when the step is done) or fi_learner_step_staged_async
  * (returns once enqueued; fi_learner_wait as above). The H2D runs on a copy stream beside
  * the previous device step. Acquiring again before submitting returns the same buffer;
- * submitting without an acquired buffer is FI_ERR_INVALID. MLP configuration only.       */
+ * submitting without an acquired buffer is FI_ERR_INVALID. Both configurations: the Atari
+ * handle's buffers hold cfg.batch * (T+1) * 28672 bytes each (two pinned, two on the device;
+ * FI_ERR_OOM with the byte count when they cannot be allocated).                          */
 int fi_learner_acquire_staging(fi_learner* l, void** dst, size_t* entry_stride);
 int fi_learner_step_staged(fi_learner* l, fi_step_stats* out);
 int fi_learner_step_staged_async(fi_learner* l);
@@ -201,6 +212,13 @@ int fi_vtrace_loss_fp32_variant(int variant, int T, int B, int A, const float* p
 int fi_ingest_records(const void* records_dev, int T, int B, int A, int D,
                       size_t entry_bytes, float* obs, float* mu, int32_t* actions,
                       float* rewards, float* discounts, void* stream);
+/* The same for Atari records (FI_ATARI_RECORD_BYTES per step): frames (T+1, B, 84, 84, 4) u8
+ * plus mu / actions / rewards / discounts. entry_bytes >= (T+1)*28672 and a multiple of 16;
+ * records_dev and frames 16-byte aligned.                                                 */
+int fi_ingest_atari_records(const void* records_dev, int T, int B, int A,
+                            size_t entry_bytes, uint8_t* frames, float* mu,
+                            int32_t* actions, float* rewards, float* discounts,
+                            void* stream);
 /* Device synthetic trajectories (Philox4x32-10; bit-identical to the oracle's generator) */
 int fi_synth_trajectories(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int D,
                           float gamma, float* obs, float* mu, int32_t* actions,

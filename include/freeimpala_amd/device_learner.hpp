@@ -8,7 +8,8 @@
 //   * DeviceLearner::step(player_index, batch) -- same parameters as
 //     Learner::trainModel (reference include/freeimpala/learner.h:32) and the same
 //     `batch` that SharedBuffer::readBatch returns (data_structures.h:267-300):
-//     M entries of S * ELEMENT_SIZE bytes, record schema in DESIGN.md section 3.
+//     M entries of S * ELEMENT_SIZE bytes, record schemas in DESIGN.md section 3 (one element
+//     per step for the MLP, 28 per step -- frame + header -- for the Atari policy).
 //   * DeviceLearner::publish(player_index, blob, version) -- the bytes and version that go
 //     into Model::update / ModelManager::updateModel (data_structures.h:141-148, 441-451);
 //     blob size == param_bytes() is the ModelManager model_size.
@@ -39,7 +40,7 @@ struct LearnerConfig {
     size_t players = 1;        // --players
     size_t batch_size = 32;    // --batch-size (M entries per step)
     size_t seq_length = 100;   // --seq-length (T); entries carry T+1 records
-    size_t entry_size = 0;     // --entry-size in ELEMENT_SIZE units (0: T+1)
+    size_t entry_size = 0;     // --entry-size in ELEMENT_SIZE units (0: T+1 records)
     std::string arch = "mlp";  // --learner-arch mlp|atari
     int num_actions = 18;      // --num-actions
     int obs_dim = 128;         // --obs-dim
@@ -55,7 +56,10 @@ struct LearnerConfig {
                                // (shard g of player p on devices[(p G + g) % n]; RCCL all-reduce)
     uint64_t seed = 42;        // --seed (parameter init)
 
-    size_t entry_records() const { return entry_size ? entry_size : seq_length + 1; }
+    // ELEMENT_SIZE units one step's record takes: 1 (MLP), 28 (Atari: 84x84x4 frame + header)
+    size_t record_elements() const { return arch == "atari" ? (size_t)FI_ATARI_RECORD_ELEMENTS : 1; }
+    // whole records an entry holds
+    size_t entry_records() const { return entry_size ? entry_size / record_elements() : seq_length + 1; }
 
     // Parses the flags above from argv (unknown flags are ignored so the reference's own
     // parser can own the rest of the command line). Throws std::invalid_argument on a
@@ -106,9 +110,13 @@ struct LearnerConfig {
         }
         if (c.players == 0 || c.batch_size == 0 || c.seq_length == 0)
             throw std::invalid_argument("--players, --batch-size and --seq-length must be > 0");
-        if (c.entry_records() < c.seq_length + 1)
-            throw std::invalid_argument("--entry-size must hold seq_length + 1 records");
         if (c.arch != "mlp" && c.arch != "atari") throw std::invalid_argument("--learner-arch: mlp|atari");
+        if (c.entry_records() < c.seq_length + 1)
+            throw std::invalid_argument(
+                c.record_elements() == 1
+                    ? std::string("--entry-size must hold seq_length + 1 records")
+                    : "--entry-size must be >= " + std::to_string(c.record_elements() * (c.seq_length + 1)) + " = " +
+                          std::to_string(c.record_elements()) + " * (seq_length + 1) for --learner-arch " + c.arch);
         if (c.optimizer != "adam" && c.optimizer != "sgd") throw std::invalid_argument("--optimizer: adam|sgd");
         if (c.publish != "fp32" && c.publish != "bf16") throw std::invalid_argument("--publish: fp32|bf16");
         if (c.data_parallel == 0 || c.batch_size % c.data_parallel != 0)

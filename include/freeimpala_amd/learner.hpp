@@ -115,10 +115,11 @@ public:
         lc.players = p;
         lc.batch_size = M;
         lc.entry_size = S;
-        if (lc.seq_length + 1 > S) {
-            log("warn", "entry size " + std::to_string(S) + " holds at most " + std::to_string(S ? S - 1 : 0) +
+        const size_t R = S / lc.record_elements();  // whole records per entry
+        if (lc.seq_length + 1 > R) {
+            log("warn", "entry size " + std::to_string(S) + " holds at most " + std::to_string(R ? R - 1 : 0) +
                             " steps + bootstrap: seq_length lowered from " + std::to_string(lc.seq_length));
-            lc.seq_length = S > 1 ? S - 1 : 1;
+            lc.seq_length = R > 1 ? R - 1 : 1;
         }
         cfg_ = lc;
         device_ = std::make_unique<DeviceLearner>(cfg_);

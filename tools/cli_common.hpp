@@ -40,6 +40,17 @@ public:
         if (!g_dump_dir.empty()) dump("batch_" + std::to_string(id_) + "_" + std::to_string(n_++) + ".bin", dst, M * stride);
         return true;
     }
+    // the readBatch readers (--learner sim, --data-parallel): the same dump, whole entries back
+    // to back
+    std::vector<std::vector<char>> readBatch(size_t M) {
+        auto batch = SharedBuffer::readBatch(M);
+        if (!batch.empty() && !g_dump_dir.empty()) {
+            std::vector<char> all;
+            for (const auto& e : batch) all.insert(all.end(), e.begin(), e.end());
+            dump("batch_" + std::to_string(id_) + "_" + std::to_string(n_++) + ".bin", all.data(), all.size());
+        }
+        return batch;
+    }
     void setId(size_t id) { id_ = id; }
 
 private:
@@ -155,7 +166,8 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
         lc = LearnerConfig::from_parser(program);
         if (!program.is_used("--seq-length")) {  // default T: what an entry / a game holds
             const size_t per_player = (P.game_steps + P.num_players - 1) / std::max<size_t>(1, P.num_players);
-            lc.seq_length = std::max<size_t>(1, std::min<size_t>({lc.seq_length, P.entry_size, per_player}) - 1);
+            lc.seq_length = std::max<size_t>(
+                1, std::min<size_t>({lc.seq_length, P.entry_size / lc.record_elements(), per_player}) - 1);
         }
     } catch (const std::exception& e) {
         const std::string msg = e.what();
@@ -174,6 +186,23 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
         std::cerr << "Game steps must be less than or equal to entry size\n";
         return 1;
     }
+    // records of more than one element (Atari: 28): each player's share of the game must fit its
+    // entry, and an explicit --seq-length is not lowered to what the entry holds but refused
+    const size_t rec = lc.record_elements();
+    if (rec > 1) {
+        if (P.entry_size < rec * (lc.seq_length + 1)) {
+            std::cerr << "--entry-size must be >= " << rec * (lc.seq_length + 1) << " = " << rec
+                      << " * (seq_length + 1) elements for --learner-arch " << lc.arch << "\n";
+            return 1;
+        }
+        const size_t per_player = (P.game_steps + P.num_players - 1) / P.num_players;
+        if (per_player * rec > P.entry_size) {
+            std::cerr << "Each player's " << per_player << " game steps need " << per_player * rec
+                      << " elements (" << rec << " per record): raise --entry-size (" << P.entry_size
+                      << ") or lower --game-steps\n";
+            return 1;
+        }
+    }
     if ((P.game_steps + P.num_players - 1) / P.num_players < lc.seq_length + 1) {
         std::cerr << "Each player needs seq_length + 1 = " << lc.seq_length + 1 << " records per game: raise "
                   << "--game-steps (" << P.game_steps << ") or lower --seq-length\n";
@@ -184,7 +213,8 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
 }
 
 // One synthetic actor's game (agent.h:34-73 with the learner's record schema instead of
-// rand() bytes): step s goes to player s % P at byte (s / P) * 1024 of that player's entry.
+// rand() bytes): step s goes to player s % P at byte (s / P) * 1024 of that player's entry
+// (MLP), or (s / P) * 28 * 1024 with the Atari record.
 class GameWriter {
 public:
     GameWriter(size_t actor_id, const Params& P, const LearnerConfig& lc)
@@ -195,22 +225,34 @@ public:
     std::vector<std::vector<char>>& play(const std::vector<uint64_t>& versions) {
         const size_t entry_bytes = P_.entry_size * ELEMENT_SIZE;
         for (auto& e : entries_) std::fill(e.begin(), e.end(), 0);
+        const size_t rec_bytes = lc_.record_elements() * ELEMENT_SIZE;
         for (size_t s = 0; s < P_.game_steps; ++s) {
             const size_t p = s % P_.num_players;
-            const size_t off = (s / P_.num_players) * ELEMENT_SIZE;
-            if (off + ELEMENT_SIZE <= entry_bytes) write_record(entries_[p].data() + off, (uint32_t)versions[p]);
+            const size_t off = (s / P_.num_players) * rec_bytes;
+            if (off + rec_bytes <= entry_bytes) write_record(entries_[p].data() + off, (uint32_t)versions[p]);
         }
         return entries_;
     }
 
 private:
     // record schema: obs[0,512) | mu logits [512,768) | action 768 |
-    // reward 772 | discount 776 | flags 780 (here: the policy version the actor held)
+    // reward 772 | discount 776 | flags 780 (here: the policy version the actor held); the Atari
+    // record puts a random u8 frame in [0, 28224) and the same header at 28224
     void write_record(char* r, uint32_t version) {
         std::normal_distribution<float> nrm(0.f, 1.f);
         std::uniform_real_distribution<float> uni(0.f, 1.f);
         float obs[128] = {}, mu[64] = {};
-        for (int d = 0; d < lc_.obs_dim; ++d) obs[d] = nrm(rng_);
+        const bool atari = lc_.arch == "atari";
+        if (atari) {  // (a branch the MLP never takes: its byte stream per seed stays as it was)
+            constexpr size_t kFrame = 84 * 84 * 4;
+            for (size_t i = 0; i < kFrame; i += 8) {
+                const uint64_t w = rng_();
+                std::memcpy(r + i, &w, 8);
+            }
+            r += kFrame;  // the header follows the frame
+        } else {
+            for (int d = 0; d < lc_.obs_dim; ++d) obs[d] = nrm(rng_);
+        }
         const int A = lc_.num_actions;
         double mx = -1e30, z = 0.0;
         for (int a = 0; a < A; ++a) mx = std::max(mx, (double)(mu[a] = nrm(rng_)));
@@ -226,12 +268,15 @@ private:
         }
         const float reward = (float)((int)(rng_() % 3) - 1);
         const float discount = uni(rng_) < 0.01f ? 0.f : lc_.gamma;
-        std::memcpy(r, obs, sizeof obs);
-        std::memcpy(r + 512, mu, sizeof mu);
-        std::memcpy(r + 768, &action, 4);
-        std::memcpy(r + 772, &reward, 4);
-        std::memcpy(r + 776, &discount, 4);
-        std::memcpy(r + 780, &version, 4);
+        if (!atari) {
+            std::memcpy(r, obs, sizeof obs);
+            r += 512;
+        }
+        std::memcpy(r, mu, sizeof mu);  // both headers: mu, then +256 action, reward, discount, flags
+        std::memcpy(r + 256, &action, 4);
+        std::memcpy(r + 260, &reward, 4);
+        std::memcpy(r + 264, &discount, 4);
+        std::memcpy(r + 268, &version, 4);
     }
 
     Params P_;

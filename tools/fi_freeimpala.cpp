@@ -10,7 +10,8 @@
 //     floor(agents * iterations / batch_size) (main.cpp:179);
 //   * agents are synthetic actors: each game writes per-step 1 KiB records in the learner's
 //     record schema at the reference's producer offsets -- step s goes to
-//     player s % P at byte (s / P) * 1024 (agent.h:48-73) -- then writes one entry per player
+//     player s % P at byte (s / P) * 1024 (agent.h:48-73), or 28 KiB Atari records (frame +
+//     header) at (s / P) * 28 * 1024 with --learner-arch atari -- then writes one entry per player
 //     into that player's SharedBuffer (agent.h:78-104), and syncs the published model when its
 //     version moved (agent.h:151-178); the record's flags word carries the policy version;
 //   * cleanup as main.cpp:233-262: join agents, stop the learner (drain + final save), print

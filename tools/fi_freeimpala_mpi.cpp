@@ -12,7 +12,8 @@
 // The reference flags and validation, the learner flags (--seq-length, --learner-arch, --lr,
 // --devices, ...) and the learner iteration count floor(agents * iterations / M)
 // (main.cpp:167-170) as in tools/fi_freeimpala.cpp. Actors write the learner's 1 KiB record
-// schema instead of rand() bytes. Only rank 0 touches a GPU.
+// schema (28 KiB Atari records with --learner-arch atari, the message
+// still S * ELEMENT_SIZE bytes) instead of rand() bytes. Only rank 0 touches a GPU.
 // Rank 0 prints one JSON line: learner iterations, the endpoint's message counts, the
 // end-to-end env-steps/s (T * M per learner step over the wall time from the first posted
 // receive to the last learner step) and the metrics summary.
