@@ -26,6 +26,17 @@ ATARI_RECORD_BYTES = 28 * 1024
 ATARI_FRAME_BYTES = 84 * 84 * 4
 ATARI_REC_FRAME, ATARI_REC_MU, ATARI_REC_ACT, ATARI_REC_REW, ATARI_REC_DISC, ATARI_REC_FLAGS = \
     0, 28224, 28480, 28484, 28488, 28492
+# the single-plane Atari record: 7 ELEMENTs per step (the newest 84x84 plane, a compact header with
+# mu[<=18]); the entry ends with the 3-plane history block (21 ELEMENTs) at (T+1) * 7168
+FI_RECORDS_STACKED, FI_RECORDS_PLANES = 0, 1
+ATARI_PLANE_RECORD_ELEMENTS = 7
+ATARI_PLANE_RECORD_BYTES = 7 * 1024
+ATARI_HISTORY_ELEMENTS = 21
+ATARI_HISTORY_BYTES = 21 * 1024
+ATARI_PLANE_BYTES = 84 * 84
+ATARI_PLANE_MAX_ACTIONS = 18
+PLANE_REC_PLANE, PLANE_REC_MU, PLANE_REC_ACT, PLANE_REC_REW, PLANE_REC_DISC, PLANE_REC_FLAGS, PLANE_REC_START = \
+    0, 7056, 7128, 7132, 7136, 7140, 7144
 
 
 class VtraceHparams(C.Structure):
@@ -64,6 +75,7 @@ SIGNATURES = {
     "fi_learner_param_bytes": ([_P], C.c_size_t),
     "fi_learner_entry_bytes": ([_P], C.c_size_t),
     "fi_learner_record_bytes": ([_P], C.c_size_t),
+    "fi_learner_set_record_format": ([_P, C.c_int], C.c_int),
     "fi_learner_step": ([_P, C.POINTER(_P), C.c_size_t, C.c_size_t, C.POINTER(StepStats)], C.c_int),
     "fi_learner_step_async": ([_P, C.POINTER(_P), C.c_size_t, C.c_size_t], C.c_int),
     "fi_learner_wait": ([_P, C.POINTER(StepStats)], C.c_int),
@@ -100,6 +112,7 @@ SIGNATURES = {
     "fi_ingest_records": ([_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t] + [_P] * 6,
                           C.c_int),
     "fi_ingest_atari_records": ([_P, C.c_int, C.c_int, C.c_int, C.c_size_t] + [_P] * 6, C.c_int),
+    "fi_ingest_atari_planes": ([_P, C.c_int, C.c_int, C.c_int, C.c_size_t] + [_P] * 6, C.c_int),
     "fi_synth_trajectories": ([C.c_uint64] + [C.c_int] * 6 + [C.c_float] + [_P] * 7, C.c_int),
 }
 

@@ -88,5 +88,10 @@ int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_byte
 int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
                         float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
                         int* bad = nullptr);
+// Atari plane records (FI_ATARI_PLANE_RECORD_BYTES per step, then the 3-plane history block): the
+// same outputs, the 4-frame stack rebuilt from single planes and episode_start; A <= 18
+int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
+                               float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
+                               int* bad = nullptr);
 
 }  // namespace fi

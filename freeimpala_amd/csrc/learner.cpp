@@ -93,6 +93,7 @@ struct fi_learner {
     bool in_flight = false;  // an async step was enqueued and not yet waited for
     size_t rec_bytes = 0;
     size_t rec_entry_bytes = 0;
+    int rec_format = FI_RECORDS_STACKED;  // Atari host entries: whole stacks, or single planes
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -343,13 +344,31 @@ extern "C" size_t fi_learner_param_bytes(const fi_learner* l) {
     if (!l) return 0;
     return l->nparams * (l->cfg.publish_dtype == FI_PUBLISH_BF16 ? 2 : 4);
 }
-// one step's record in a host entry: a 1 KiB ELEMENT (MLP), 28 of them (Atari: frame + header)
+// one step's record in a host entry: a 1 KiB ELEMENT (MLP), 28 of them (Atari: frame + header),
+// 7 (Atari planes: the newest plane + header)
 static size_t record_bytes(const fi_learner* l) {
-    return l->cfg.arch == FI_ARCH_ATARI ? (size_t)FI_ATARI_RECORD_BYTES : (size_t)FI_RECORD_BYTES;
+    if (l->cfg.arch != FI_ARCH_ATARI) return (size_t)FI_RECORD_BYTES;
+    return l->rec_format == FI_RECORDS_PLANES ? (size_t)FI_ATARI_PLANE_RECORD_BYTES : (size_t)FI_ATARI_RECORD_BYTES;
 }
+// what follows an entry's T+1 records: the history block of the planes format
+static size_t entry_tail_bytes(const fi_learner* l) {
+    return l->cfg.arch == FI_ARCH_ATARI && l->rec_format == FI_RECORDS_PLANES ? (size_t)FI_ATARI_HISTORY_BYTES : 0;
+}
+static size_t entry_bytes_min(const fi_learner* l) { return (size_t)(l->T + 1) * record_bytes(l) + entry_tail_bytes(l); }
 extern "C" size_t fi_learner_record_bytes(const fi_learner* l) { return l ? record_bytes(l) : 0; }
-extern "C" size_t fi_learner_entry_bytes(const fi_learner* l) {
-    return l ? (size_t)(l->T + 1) * record_bytes(l) : 0;
+extern "C" size_t fi_learner_entry_bytes(const fi_learner* l) { return l ? entry_bytes_min(l) : 0; }
+extern "C" int fi_learner_set_record_format(fi_learner* l, int fmt) {
+    FI_REQUIRE(l, "set_record_format: null learner");
+    FI_REQUIRE(l->cfg.arch == FI_ARCH_ATARI, "set_record_format: only the Atari policy has record formats");
+    FI_REQUIRE(fmt == FI_RECORDS_STACKED || fmt == FI_RECORDS_PLANES, "set_record_format: unknown format");
+    FI_REQUIRE(fmt != FI_RECORDS_PLANES || l->A <= 18,
+               "set_record_format: the plane record's header holds mu[18]: num_actions = " + std::to_string(l->A) +
+                   " > 18 needs the stacked format");
+    if (l->rec_bytes != 0)
+        return fail(FI_ERR_STATE, "set_record_format: the staging buffers exist (choose the format before the "
+                                  "first host batch)");
+    l->rec_format = fmt;
+    return FI_OK;
 }
 extern "C" void* fi_learner_stream(fi_learner* l) { return l ? (void*)l->stream : nullptr; }
 extern "C" int fi_learner_sync(fi_learner* l) {
@@ -583,6 +602,9 @@ static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out) {
             if (l->cfg.arch == FI_ARCH_MLP)
                 FI_TRY(ingest_launch(l->rec_slot[s], l->T, l->B, l->A, l->D, l->rec_entry_bytes, l->obs,
                                      l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
+            else if (l->rec_format == FI_RECORDS_PLANES)
+                FI_TRY(ingest_atari_planes_launch(l->rec_slot[s], l->T, l->B, l->A, l->rec_entry_bytes,
+                                                  l->frames, l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
             else
                 // frames (like mu / act / rew / disc) is rewritten in place: every kernel that
                 // read it in the previous step -- the forward and the backward's conv1 weight
@@ -706,7 +728,7 @@ static void parallel_copy(char* dst, const void* const* entries, size_t n, size_
 // H2D that last read it is done; submit_slot() enqueues its H2D on the copy stream (after the
 // ingest that last read the device slot) and makes it the batch the next run_step ingests.
 static int ensure_staging(fi_learner* l) {
-    const size_t need = (size_t)(l->T + 1) * record_bytes(l);
+    const size_t need = entry_bytes_min(l);
     const size_t bytes = (size_t)l->B * need;
     if (bytes <= l->rec_bytes) return FI_OK;
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
@@ -781,9 +803,10 @@ static int submit_slot(fi_learner* l) {
 static int stage_entries(fi_learner* l, const void* const* entries, size_t n_entries, size_t entry_bytes) {
     FI_REQUIRE(l && entries, "step: null argument");
     FI_REQUIRE(n_entries == (size_t)l->B, "step: n_entries must equal the configured batch");
-    const size_t need = (size_t)(l->T + 1) * record_bytes(l);
+    const size_t need = entry_bytes_min(l);
     FI_REQUIRE(entry_bytes >= need, "step: entry_bytes " + std::to_string(entry_bytes) + " < " +
-                                        std::to_string(need) + " = (T+1)*" + std::to_string(record_bytes(l)));
+                                        std::to_string(need) + " = (T+1)*" + std::to_string(record_bytes(l)) +
+                                        (entry_tail_bytes(l) ? " + " + std::to_string(entry_tail_bytes(l)) : ""));
     for (size_t i = 0; i < n_entries; ++i) FI_REQUIRE(entries[i], "step: null entry");
     FI_HIP_CHECK(hipSetDevice(l->dev));
     int s = 0;

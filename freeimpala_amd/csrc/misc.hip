@@ -1,7 +1,8 @@
 // misc.hip -- HBM-bound helper kernels of the learner step (gfx950):
 //   * synthetic trajectories (Philox4x32-10, bit-identical to the oracle's generator)
-//   * ingest: (B, S*1024) SharedBuffer entries -> time-major SoA tensors (MLP records, and the
-//     Atari records with their 84x84x4 frames)
+//   * ingest: (B, S*1024) SharedBuffer entries -> time-major SoA tensors (MLP records, the
+//     Atari records with their 84x84x4 frames, and the single-plane Atari records whose
+//     4-frame stack is rebuilt here)
 //   * column sums / split-K slab reduction (deterministic, fixed order)
 //   * global gradient norm, Adam / SGD with global-norm clipping, fp32 -> bf16
 #include <algorithm>
@@ -120,12 +121,18 @@ int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int 
 //   28484 float reward | 28488 float discount | 28492 uint32 flags | 28496.. reserved.
 // Both headers have the same shape: mu, then action / reward / discount at +256 / +260 / +264.
 // An entry holds T+1 records (record T = bootstrap observation; its header is ignored).
+// Atari plane record schema (7 ELEMENTs = 7,168 B per step, FI_ATARI_PLANE_RECORD_BYTES):
+//   [0,7056) u8 plane 84x84 (the newest observation) | [7056,7128) float mu_logits[<=18] |
+//   7128 int32 action | 7132 float reward | 7136 float discount | 7140 uint32 flags |
+//   7144 uint32 episode_start | 7148.. reserved.
+// Its entry holds T+1 records and then, at (T+1)*7168, the three planes that precede record 0 in
+// the actor's stack (oldest first, 3*7056 B, padded to FI_ATARI_HISTORY_BYTES).
 constexpr int REC_OBS = 0, REC_MU = 512;
-constexpr int HDR_ACT = 256, HDR_REW = 260, HDR_DISC = 264;  // relative to the record's mu
+constexpr int HDR_ACT = 256;  // relative to the record's mu; reward and discount follow the action
 constexpr int kFrameBytes = 84 * 84 * 4;
 constexpr int kFramePieces = kFrameBytes / 16;  // 1,764 16-byte pieces
 constexpr int ATARI_REC_MU = kFrameBytes;
-static_assert(ATARI_REC_MU + HDR_DISC + 8 <= FI_ATARI_RECORD_BYTES, "Atari record header");
+static_assert(ATARI_REC_MU + HDR_ACT + 16 <= FI_ATARI_RECORD_BYTES, "Atari record header");
 static_assert(FI_ATARI_RECORD_BYTES == FI_ATARI_RECORD_ELEMENTS * FI_RECORD_BYTES, "Atari record size");
 
 __global__ void ingest_vec_kernel(const char* __restrict__ rec, int rows, int B, int W,
@@ -143,18 +150,19 @@ __global__ void ingest_vec_kernel(const char* __restrict__ rec, int rows, int B,
 }
 
 __global__ void ingest_scalar_kernel(const char* __restrict__ rec, int T, int B, int A,
-                                     int mu_off, size_t rec_stride, size_t entry_bytes,
+                                     int mu_off, int hdr_act, size_t rec_stride, size_t entry_bytes,
                                      int32_t* act, float* rew, float* disc, int* bad) {
     const size_t n = (size_t)T * B;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
          i += (size_t)gridDim.x * blockDim.x) {
         const int t = (int)(i / B), b = (int)(i - (size_t)t * B);
         const char* r = rec + (size_t)b * entry_bytes + (size_t)t * rec_stride + mu_off;
-        int32_t a = *(const int32_t*)(r + HDR_ACT);
+        r += hdr_act;
+        int32_t a = *(const int32_t*)r;
         if ((unsigned)a >= (unsigned)A && bad) atomicAdd(bad, 1);
         act[i] = a < 0 ? 0 : (a >= A ? A - 1 : a);
-        rew[i] = *(const float*)(r + HDR_REW);
-        disc[i] = *(const float*)(r + HDR_DISC);
+        rew[i] = *(const float*)(r + 4);
+        disc[i] = *(const float*)(r + 8);
     }
 }
 
@@ -200,7 +208,7 @@ int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_byte
                            B, A, REC_MU, stride, entry_bytes, mu);
     if (act && rew && disc)
         hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T,
-                           B, A, REC_MU, stride, entry_bytes, act, rew, disc, bad);
+                           B, A, REC_MU, HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -227,7 +235,116 @@ int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes
     hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T, B, A,
                        ATARI_REC_MU, stride, entry_bytes, mu);
     hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T, B, A,
-                       ATARI_REC_MU, stride, entry_bytes, act, rew, disc, bad);
+                       ATARI_REC_MU, HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+// Plane records -> the same frames tensor: channel c of frame t is the plane of step t-3+c, the
+// first observation of an episode filling all four channels (the frame-stack wrapper's rule,
+// DESIGN.md section 3). A byte interleave of four planes into 4-byte pixels that reads every
+// plane from HBM once.
+//   A one-wave workgroup owns an entry b and a run of 64 16-byte plane pieces (1,024 pixels) and
+// walks t forward: -3..-1 take the history block's planes, 0..T the records'. Each step a lane
+// loads its 16-byte piece (the next step's is requested before this step's stores), the wave
+// turns the 256 dwords through LDS so that lane j holds dwords 64k + j (k = 0..3), and the lane
+// keeps the three previous steps' four dwords in registers. Output piece 64k + j of the run is
+// then the byte interleave of dword 64k + j of the four channels (two levels of v_perm_b32), so
+// each of the four 16-byte stores of a step is contiguous over the wave (1 KiB). episode_start
+// is uniform per (t, b): one scalar load and a uniform branch. 7 runs cover the 441 pieces (the
+// last has 57); 7 B workgroups, no grid cap.
+constexpr int PLANE_REC = FI_ATARI_PLANE_RECORD_BYTES;
+constexpr int kPlaneBytes = 84 * 84;
+constexpr int kPlanePieces = kPlaneBytes / 16;                // 441 16-byte pieces per plane
+constexpr int kPlaneRuns = (kPlanePieces + 63) / 64;          // 7 runs of 64 pieces
+constexpr int PLANE_REC_MU = kPlaneBytes, PLANE_HDR_ACT = 72;  // action at 7128, +4 reward, +8 discount
+constexpr int PLANE_REC_START = 7144;
+constexpr int kPlaneMaxActions = 18;
+static_assert(kPlanePieces * 16 == kPlaneBytes, "a plane is a whole number of 16-byte pieces");
+static_assert(PLANE_REC_MU + 4 * kPlaneMaxActions == PLANE_REC_MU + PLANE_HDR_ACT, "compact header: mu[18], action");
+static_assert(PLANE_REC_START + 4 <= PLANE_REC, "plane record header");
+static_assert(PLANE_REC == FI_ATARI_PLANE_RECORD_ELEMENTS * FI_RECORD_BYTES, "plane record size");
+static_assert(3 * kPlaneBytes <= FI_ATARI_HISTORY_BYTES &&
+                  FI_ATARI_HISTORY_BYTES == FI_ATARI_HISTORY_ELEMENTS * FI_RECORD_BYTES, "history block");
+
+// 4 pixels of channels 0..3 (one dword each) -> 4 NHWC pixels (byte c of a pixel = channel c)
+__device__ __forceinline__ uint4 interleave4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    const uint32_t ab_lo = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
+    const uint32_t ab_hi = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
+    const uint32_t cd_lo = __builtin_amdgcn_perm(d, c, 0x05010400u);
+    const uint32_t cd_hi = __builtin_amdgcn_perm(d, c, 0x07030602u);
+    return make_uint4(__builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u),   // a0 b0 c0 d0
+                      __builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u),   // a1 b1 c1 d1
+                      __builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u),
+                      __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u));
+}
+
+__global__ __launch_bounds__(64) void ingest_planes_kernel(const char* __restrict__ rec, int T, int B,
+                                                           size_t entry_bytes, uint4* __restrict__ frames) {
+    __shared__ uint4 turn[2][64];  // two buffers: one barrier per step
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x / kPlaneRuns, run = blockIdx.x - b * kPlaneRuns;
+    const int piece = run * 64 + lane;
+    const bool live = piece < kPlanePieces;  // the loads of the last run's 7 spare lanes are skipped
+    const char* __restrict__ entry = rec + (size_t)b * entry_bytes;
+    const uint4* __restrict__ hist = (const uint4*)(entry + (size_t)(T + 1) * PLANE_REC);
+    uint32_t w0[4] = {}, w1[4] = {}, w2[4] = {};  // this lane's dwords of the three previous steps
+    uint4 next = make_uint4(0u, 0u, 0u, 0u);
+    if (live) next = hist[piece];
+    for (int t = -3; t <= T; ++t) {
+        const uint4 cur = next;
+        if (t < T && live) {
+            const uint4* src = t + 1 < 0 ? hist + (t + 4) * kPlanePieces
+                                         : (const uint4*)(entry + (size_t)(t + 1) * PLANE_REC);
+            next = src[piece];
+        }
+        uint4* x = turn[t & 1];
+        x[lane] = cur;
+        __syncthreads();
+        const uint32_t* xd = (const uint32_t*)x;
+        uint32_t n[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) n[k] = xd[64 * k + lane];
+        if (t >= 0) {
+            if (*(const uint32_t*)(entry + (size_t)t * PLANE_REC + PLANE_REC_START) != 0u) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w0[k] = w1[k] = w2[k] = n[k];
+            }
+            uint4* __restrict__ dst = frames + ((size_t)t * B + b) * kFramePieces + run * 256 + lane;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (run * 256 + 64 * k + lane < kFramePieces) dst[64 * k] = interleave4(w0[k], w1[k], w2[k], n[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w0[k] = w1[k];
+            w1[k] = w2[k];
+            w2[k] = n[k];
+        }
+    }
+}
+
+int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
+                               float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad) {
+    FI_REQUIRE(rec && frames && mu && act && rew && disc, "ingest_atari_planes: null argument");
+    FI_REQUIRE(T >= 1 && B >= 1 && A >= 1, "ingest_atari_planes: bad shape");
+    FI_REQUIRE(A <= kPlaneMaxActions, "ingest_atari_planes: the plane record's header holds mu[18]: A = " +
+                                          std::to_string(A) + " > 18");
+    FI_REQUIRE((size_t)(T + 1) * (size_t)B <= (size_t)0x7fffffff / kPlaneRuns, "ingest_atari_planes: too many frames");
+    FI_REQUIRE(entry_bytes % 16 == 0, "ingest_atari_planes: entry_bytes must be a multiple of 16");
+    const size_t need = (size_t)(T + 1) * PLANE_REC + FI_ATARI_HISTORY_BYTES;
+    FI_REQUIRE(entry_bytes >= need, "ingest_atari_planes: entry_bytes < " + std::to_string(need) +
+                                        " = (T+1)*7168 + 21504");
+    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)frames % 16 == 0,
+               "ingest_atari_planes: records and frames must be 16-byte aligned");
+    const char* r = (const char*)rec;
+    const size_t stride = PLANE_REC;
+    hipLaunchKernelGGL(ingest_planes_kernel, dim3((unsigned)(B * kPlaneRuns)), dim3(64), 0, s, r, T, B, entry_bytes,
+                       (uint4*)frames);
+    hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T, B, A,
+                       PLANE_REC_MU, stride, entry_bytes, mu);
+    hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T, B, A,
+                       PLANE_REC_MU, PLANE_HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -512,4 +629,11 @@ extern "C" int fi_ingest_atari_records(const void* rec, int T, int B, int A, siz
                                        float* disc, void* stream) {
     return fi::ingest_atari_launch(rec, T, B, A, entry_bytes, frames, mu, act, rew, disc,
                                    (hipStream_t)stream);
+}
+
+extern "C" int fi_ingest_atari_planes(const void* rec, int T, int B, int A, size_t entry_bytes,
+                                      uint8_t* frames, float* mu, int32_t* act, float* rew,
+                                      float* disc, void* stream) {
+    return fi::ingest_atari_planes_launch(rec, T, B, A, entry_bytes, frames, mu, act, rew, disc,
+                                          (hipStream_t)stream);
 }

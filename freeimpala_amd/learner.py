@@ -39,7 +39,10 @@ def _as_host_batch(batch) -> HostBatch:
 class DeviceLearner:
     def __init__(self, arch: str = "mlp", seq_len: int = 100, batch: int = 32,
                  num_actions: int = 18, obs_dim: int = 128, hidden: int = 256,
-                 optimizer: str = "adam", publish: str = "fp32", device: int = 0, **kw):
+                 optimizer: str = "adam", publish: str = "fp32", device: int = 0,
+                 records: str = "stacked", **kw):
+        if records not in ("stacked", "planes"):
+            raise ValueError(f"records: stacked | planes, not {records!r}")
         self.cfg = _abi.default_config(
             arch=_abi.FI_ARCH_MLP if arch == "mlp" else _abi.FI_ARCH_ATARI, seq_len=seq_len,
             batch=batch, num_actions=num_actions, obs_dim=obs_dim, hidden=hidden,
@@ -51,6 +54,13 @@ class DeviceLearner:
         self.T, self.B, self.A = seq_len, batch, num_actions
         self.D, self.H = obs_dim, hidden
         self.arch = arch
+        self.records = records
+        if records == "planes":  # host entries carry single planes
+            try:
+                self.set_record_format(_abi.FI_RECORDS_PLANES)
+            except Exception:
+                self.close()
+                raise
 
     # --- sizes
     @property
@@ -67,8 +77,14 @@ class DeviceLearner:
 
     @property
     def record_bytes(self) -> int:
-        """Bytes of one step's record in a host entry: 1024 (MLP), 28672 (Atari)."""
+        """Bytes of one step's record in a host entry: 1024 (MLP), 28672 (Atari), 7168 (Atari
+        plane records)."""
         return int(lib().fi_learner_record_bytes(self._h))
+
+    def set_record_format(self, fmt: int) -> None:
+        """fi_learner_set_record_format: _abi.FI_RECORDS_STACKED | FI_RECORDS_PLANES, before the
+        first host batch."""
+        check(lib().fi_learner_set_record_format(self._h, fmt), "fi_learner_set_record_format")
 
     # --- the step
     def step(self, batch: Sequence[bytes | bytearray | np.ndarray] | HostBatch,
@@ -342,3 +358,107 @@ def unpack_atari_records(batch_bytes, T, B, A):
     rew = field(_abi.ATARI_REC_REW, 1, np.float32)[..., 0]
     disc = field(_abi.ATARI_REC_DISC, 1, np.float32)[..., 0]
     return frames, mu, np.ascontiguousarray(act), np.ascontiguousarray(rew), np.ascontiguousarray(disc)
+
+
+def _u8_rows(batch_bytes, B):
+    if isinstance(batch_bytes, (bytes, bytearray, memoryview, np.ndarray)):
+        buf = np.frombuffer(batch_bytes, np.uint8) if not isinstance(batch_bytes, np.ndarray) \
+            else np.ascontiguousarray(batch_bytes).view(np.uint8).ravel()
+    else:
+        buf = np.concatenate([np.frombuffer(e, np.uint8) if not isinstance(e, np.ndarray)
+                              else np.ascontiguousarray(e).view(np.uint8).ravel() for e in batch_bytes])
+    if buf.size % B:
+        raise ValueError(f"{buf.size} bytes are not {B} entries of equal length")
+    return buf.reshape(B, -1)
+
+
+def plane_entry_elements(T: int) -> int:
+    """--entry-size of a plane-record entry: 7 per record, T+1 records, the 21-element history."""
+    return _abi.ATARI_PLANE_RECORD_ELEMENTS * (T + 1) + _abi.ATARI_HISTORY_ELEMENTS
+
+
+def pack_atari_plane_records(planes, history, episode_start, mu, actions, rewards, discounts,
+                             entry_size=None) -> list[bytes]:
+    """Build SharedBuffer entries of single-plane Atari records (inverse of the planes ingest's
+    header and plane reads). planes (T+1,B,84,84) uint8: the newest observation of every step;
+    history (3,B,84,84) uint8: the planes preceding record 0, oldest first; episode_start (T+1,B)
+    bool; mu (T,B,A<=18), actions/rewards/discounts (T,B). Returns B entries of entry_size*1024
+    bytes (default 7*(T+1)+21): T+1 records, then the history block at (T+1)*7168."""
+    planes = np.asarray(planes, np.uint8)
+    T1, B = planes.shape[:2]
+    T = T1 - 1
+    A = mu.shape[-1]
+    if A > _abi.ATARI_PLANE_MAX_ACTIONS:
+        raise ValueError(f"the plane record's header holds mu[18]: A = {A}")
+    R, PB = _abi.ATARI_PLANE_RECORD_BYTES, _abi.ATARI_PLANE_BYTES
+    S = entry_size or plane_entry_elements(T)
+    if S < plane_entry_elements(T):
+        raise ValueError(f"entry_size {S} < {plane_entry_elements(T)} = 7*(T+1)+21")
+    pl = planes.reshape(T1, B, PB)
+    hi = np.asarray(history, np.uint8).reshape(3, B, PB)
+    es = np.asarray(episode_start).reshape(T1, B) != 0
+    out = []
+    for b in range(B):
+        e = np.zeros(S * 1024, np.uint8)
+        rec = e[:T1 * R].reshape(T1, R)
+        rec[:, :PB] = pl[:, b]
+        rec[:, _abi.PLANE_REC_START:_abi.PLANE_REC_START + 4] = es[:, b].astype(np.uint32).view(np.uint8).reshape(T1, 4)
+        h = rec[:T]
+        h[:, _abi.PLANE_REC_MU:_abi.PLANE_REC_MU + 4 * A] = \
+            np.ascontiguousarray(mu[:, b, :], np.float32).view(np.uint8).reshape(T, 4 * A)
+        for off, a, dt in ((_abi.PLANE_REC_ACT, actions, np.int32), (_abi.PLANE_REC_REW, rewards, np.float32),
+                           (_abi.PLANE_REC_DISC, discounts, np.float32)):
+            h[:, off:off + 4] = np.ascontiguousarray(a[:, b], dt).view(np.uint8).reshape(T, 4)
+        e[T1 * R:T1 * R + 3 * PB] = hi[:, b].reshape(-1)
+        out.append(e.tobytes())
+    return out
+
+
+def unpack_atari_plane_records(batch_bytes, T, B, A):
+    """Inverse of pack_atari_plane_records: B entries (a sequence, or one buffer holding them back
+    to back) -> (planes (T+1,B,84,84) uint8, history (3,B,84,84) uint8, episode_start (T+1,B) bool,
+    mu (T,B,A) float32, actions (T,B) int32, rewards (T,B), discounts (T,B) float32)."""
+    rows = _u8_rows(batch_bytes, B)
+    R, PB = _abi.ATARI_PLANE_RECORD_BYTES, _abi.ATARI_PLANE_BYTES
+    need = (T + 1) * R + _abi.ATARI_HISTORY_BYTES
+    if rows.shape[1] < need:
+        raise ValueError(f"{rows.size} bytes do not hold {B} entries of >= {need} bytes")
+    rec = rows[:, :(T + 1) * R].reshape(B, T + 1, R)
+    planes = np.ascontiguousarray(rec[:, :, :PB].transpose(1, 0, 2)).reshape(T + 1, B, 84, 84)
+    history = np.ascontiguousarray(
+        rows[:, (T + 1) * R:(T + 1) * R + 3 * PB].reshape(B, 3, PB).transpose(1, 0, 2)).reshape(3, B, 84, 84)
+
+    def field(r, off, n, dt):
+        return np.ascontiguousarray(r[:, :, off:off + 4 * n].transpose(1, 0, 2)).view(dt)
+
+    start = field(rec, _abi.PLANE_REC_START, 1, np.uint32)[..., 0] != 0
+    h = rec[:, :T]
+    mu = field(h, _abi.PLANE_REC_MU, A, np.float32)
+    act = field(h, _abi.PLANE_REC_ACT, 1, np.int32)[..., 0]
+    rew = field(h, _abi.PLANE_REC_REW, 1, np.float32)[..., 0]
+    disc = field(h, _abi.PLANE_REC_DISC, 1, np.float32)[..., 0]
+    return (planes, history, start, mu, np.ascontiguousarray(act), np.ascontiguousarray(rew),
+            np.ascontiguousarray(disc))
+
+
+def stack_planes(planes, history, episode_start) -> np.ndarray:
+    """The frame-stack wrapper, step by step: frames (T+1,B,84,84,4) uint8 from planes
+    (T+1,B,84,84), history (3,B,84,84; oldest first) and episode_start (T+1,B). A four-deep
+    window per entry slides one plane per step; the first observation of an episode fills the
+    whole window. Channel 3 is the newest plane."""
+    planes = np.asarray(planes, np.uint8)
+    history = np.asarray(history, np.uint8)
+    start = np.asarray(episode_start) != 0
+    T1, B = planes.shape[:2]
+    frames = np.empty((T1, B, 84, 84, 4), np.uint8)
+    for b in range(B):
+        window = [history[0, b], history[1, b], history[2, b], None]
+        for t in range(T1):
+            if start[t, b]:
+                window = [planes[t, b]] * 4
+            else:
+                window[3] = planes[t, b]
+            for c in range(4):
+                frames[t, b, :, :, c] = window[c]
+            window = window[1:] + [None]
+    return frames

@@ -31,6 +31,13 @@ extern "C" {
  * (record schema: DESIGN.md section 3).                                                    */
 #define FI_ATARI_RECORD_ELEMENTS 28
 #define FI_ATARI_RECORD_BYTES 28672
+/* The single-plane Atari record (FI_RECORDS_PLANES): the newest 84x84 u8 plane (7,056 B) and a
+ * compact header in 7 ELEMENTs; the entry ends with a history block of the three planes that
+ * precede record 0, padded to 21 ELEMENTs. The ingest rebuilds the 4-frame stack on the device. */
+#define FI_ATARI_PLANE_RECORD_ELEMENTS 7
+#define FI_ATARI_PLANE_RECORD_BYTES 7168
+#define FI_ATARI_HISTORY_ELEMENTS 21
+#define FI_ATARI_HISTORY_BYTES 21504
 
 enum fi_status {
     FI_OK = 0,
@@ -46,6 +53,9 @@ enum fi_status {
 enum fi_arch { FI_ARCH_MLP = 0, FI_ARCH_ATARI = 1 };
 enum fi_optimizer { FI_OPT_ADAM = 0, FI_OPT_SGD = 1 };
 enum fi_publish { FI_PUBLISH_FP32 = 0, FI_PUBLISH_BF16 = 1 };
+/* what an Atari handle's host entries hold per step: the whole 84x84x4 stack (default), or the
+ * newest plane only (fi_learner_set_record_format)                                          */
+enum fi_record_format { FI_RECORDS_STACKED = 0, FI_RECORDS_PLANES = 1 };
 
 /* V-trace / IMPALA loss hyper-parameters (IMPALA defaults). */
 typedef struct fi_vtrace_hparams {
@@ -93,20 +103,27 @@ int fi_learner_create(const fi_learner_config* cfg, fi_learner** out);
 void fi_learner_destroy(fi_learner* l);
 const char* fi_last_error(void);
 int fi_abi_version(void);
+/* Chooses the host entry format of an Atari handle, before its first host batch. FI_ERR_INVALID
+ * on an MLP handle, an unknown format, or FI_RECORDS_PLANES with num_actions > 18 (the plane
+ * record's header holds mu[18]); FI_ERR_STATE once the handle's staging buffers exist.      */
+int fi_learner_set_record_format(fi_learner* l, int fmt);
 
 /* ---- sizes ------------------------------------------------------------------------ */
 size_t fi_learner_param_count(const fi_learner* l);  /* fp32 parameters              */
 size_t fi_learner_param_bytes(const fi_learner* l);  /* published blob (fp32|bf16)   */
 size_t fi_learner_record_bytes(const fi_learner* l); /* one step's record: 1024 (MLP),
-                                                        28672 (Atari)                */
+                                                        28672 (Atari), 7168 (Atari planes) */
 size_t fi_learner_entry_bytes(const fi_learner* l);  /* minimum per entry:
-                                                        (T+1) * fi_learner_record_bytes */
+                                                        (T+1) * fi_learner_record_bytes, plus
+                                                        the 21504-byte history block of a
+                                                        planes handle                  */
 
 /* ---- the learner step ---------------------------------------------------------------
  * fi_learner_step: Learner::step(player, batch) body. entries[i] points at one
  * SharedBuffer entry (host memory, borrowed for the call only; entry_bytes >=
  * fi_learner_entry_bytes(): (T+1)*1024 for the MLP, (T+1)*28672 and a multiple of 16 for the
- * Atari policy; record schemas in DESIGN.md section 3). n_entries must equal cfg.batch. Only
+ * Atari policy, (T+1)*7168 + 21504 and a multiple of 16 for its planes format; record schemas in
+ * DESIGN.md section 3). n_entries must equal cfg.batch. Only
  * the first fi_learner_entry_bytes() bytes of each entry are read. The call stages
  * the batch (pinned copy + async H2D), runs ingest -> policy fwd -> V-trace/loss -> bwd
  * -> [RCCL all-reduce] -> optimizer, and returns when the step has completed.
@@ -135,8 +152,9 @@ int fi_learner_wait(fi_learner* l, fi_step_stats* out);
  * (returns once enqueued; fi_learner_wait as above). The H2D runs on a copy stream beside
  * the previous device step. Acquiring again before submitting returns the same buffer;
  * submitting without an acquired buffer is FI_ERR_INVALID. Both configurations: the Atari
- * handle's buffers hold cfg.batch * (T+1) * 28672 bytes each (two pinned, two on the device;
- * FI_ERR_OOM with the byte count when they cannot be allocated).                          */
+ * handle's buffers hold cfg.batch * (T+1) * 28672 bytes each, cfg.batch * ((T+1) * 7168 + 21504)
+ * in the planes format (two pinned, two on the device; FI_ERR_OOM with the byte count when they
+ * cannot be allocated).                                                                     */
 int fi_learner_acquire_staging(fi_learner* l, void** dst, size_t* entry_stride);
 int fi_learner_step_staged(fi_learner* l, fi_step_stats* out);
 int fi_learner_step_staged_async(fi_learner* l);
@@ -219,6 +237,13 @@ int fi_ingest_atari_records(const void* records_dev, int T, int B, int A,
                             size_t entry_bytes, uint8_t* frames, float* mu,
                             int32_t* actions, float* rewards, float* discounts,
                             void* stream);
+/* The same for Atari plane records (FI_ATARI_PLANE_RECORD_BYTES per step, the history block at
+ * (T+1)*7168): the frames tensor is rebuilt from single planes and episode_start (DESIGN.md
+ * section 3). A <= 18; entry_bytes >= (T+1)*7168 + 21504 and a multiple of 16; records_dev and
+ * frames 16-byte aligned.                                                                  */
+int fi_ingest_atari_planes(const void* records_dev, int T, int B, int A, size_t entry_bytes,
+                           uint8_t* frames, float* mu, int32_t* actions, float* rewards,
+                           float* discounts, void* stream);
 /* Device synthetic trajectories (Philox4x32-10; bit-identical to the oracle's generator) */
 int fi_synth_trajectories(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int D,
                           float gamma, float* obs, float* mu, int32_t* actions,

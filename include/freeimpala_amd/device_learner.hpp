@@ -9,7 +9,9 @@
 //     Learner::trainModel (reference include/freeimpala/learner.h:32) and the same
 //     `batch` that SharedBuffer::readBatch returns (data_structures.h:267-300):
 //     M entries of S * ELEMENT_SIZE bytes, record schemas in DESIGN.md section 3 (one element
-//     per step for the MLP, 28 per step -- frame + header -- for the Atari policy).
+//     per step for the MLP, 28 per step -- frame + header -- for the Atari policy, or with
+//     --atari-records planes 7 per step -- newest plane + header -- and a 21-element history
+//     block after the T+1 records).
 //   * DeviceLearner::publish(player_index, blob, version) -- the bytes and version that go
 //     into Model::update / ModelManager::updateModel (data_structures.h:141-148, 441-451);
 //     blob size == param_bytes() is the ModelManager model_size.
@@ -42,6 +44,7 @@ struct LearnerConfig {
     size_t seq_length = 100;   // --seq-length (T); entries carry T+1 records
     size_t entry_size = 0;     // --entry-size in ELEMENT_SIZE units (0: T+1 records)
     std::string arch = "mlp";  // --learner-arch mlp|atari
+    std::string atari_records = "stacked";  // --atari-records stacked|planes (atari only)
     int num_actions = 18;      // --num-actions
     int obs_dim = 128;         // --obs-dim
     int hidden = 256;          // --hidden
@@ -56,10 +59,27 @@ struct LearnerConfig {
                                // (shard g of player p on devices[(p G + g) % n]; RCCL all-reduce)
     uint64_t seed = 42;        // --seed (parameter init)
 
-    // ELEMENT_SIZE units one step's record takes: 1 (MLP), 28 (Atari: 84x84x4 frame + header)
-    size_t record_elements() const { return arch == "atari" ? (size_t)FI_ATARI_RECORD_ELEMENTS : 1; }
-    // whole records an entry holds
-    size_t entry_records() const { return entry_size ? entry_size / record_elements() : seq_length + 1; }
+    bool planes() const { return arch == "atari" && atari_records == "planes"; }
+    // ELEMENT_SIZE units one step's record takes: 1 (MLP), 28 (Atari: 84x84x4 frame + header),
+    // 7 (Atari plane records: the newest 84x84 plane + header)
+    size_t record_elements() const {
+        if (arch != "atari") return 1;
+        return planes() ? (size_t)FI_ATARI_PLANE_RECORD_ELEMENTS : (size_t)FI_ATARI_RECORD_ELEMENTS;
+    }
+    // ELEMENT_SIZE units after an entry's records: the history block of the plane records
+    size_t entry_tail_elements() const { return planes() ? (size_t)FI_ATARI_HISTORY_ELEMENTS : 0; }
+    // whole records an entry holds (beside its tail)
+    size_t entry_records() const { return records_in(entry_size ? entry_size : min_entry_size()); }
+    size_t records_in(size_t elements) const {
+        return elements > entry_tail_elements() ? (elements - entry_tail_elements()) / record_elements() : 0;
+    }
+    // the smallest --entry-size for seq_length + 1 records
+    size_t min_entry_size() const { return record_elements() * (seq_length + 1) + entry_tail_elements(); }
+    // "28 * (seq_length + 1)", "7 * (seq_length + 1) + 21"
+    std::string min_entry_size_formula() const {
+        return std::to_string(record_elements()) + " * (seq_length + 1)" +
+               (entry_tail_elements() ? " + " + std::to_string(entry_tail_elements()) : "");
+    }
 
     // Parses the flags above from argv (unknown flags are ignored so the reference's own
     // parser can own the rest of the command line). Throws std::invalid_argument on a
@@ -83,6 +103,7 @@ struct LearnerConfig {
             else if (f == "--seq-length") c.seq_length = (size_t)num(f, v);
             else if (f == "--entry-size" || f == "-S") c.entry_size = (size_t)num(f, v);
             else if (f == "--learner-arch") c.arch = v;
+            else if (f == "--atari-records") c.atari_records = v;
             else if (f == "--num-actions") c.num_actions = (int)num(f, v);
             else if (f == "--obs-dim") c.obs_dim = (int)num(f, v);
             else if (f == "--hidden") c.hidden = (int)num(f, v);
@@ -111,12 +132,20 @@ struct LearnerConfig {
         if (c.players == 0 || c.batch_size == 0 || c.seq_length == 0)
             throw std::invalid_argument("--players, --batch-size and --seq-length must be > 0");
         if (c.arch != "mlp" && c.arch != "atari") throw std::invalid_argument("--learner-arch: mlp|atari");
+        if (c.atari_records != "stacked" && c.atari_records != "planes")
+            throw std::invalid_argument("--atari-records: stacked|planes");
+        if (c.atari_records != "stacked" && c.arch != "atari")
+            throw std::invalid_argument("--atari-records planes needs --learner-arch atari");
+        if (c.planes() && c.num_actions > 18)
+            throw std::invalid_argument("--atari-records planes: the plane record's header holds mu[18], --num-actions " +
+                                        std::to_string(c.num_actions) + " > 18 needs stacked records");
         if (c.entry_records() < c.seq_length + 1)
             throw std::invalid_argument(
                 c.record_elements() == 1
                     ? std::string("--entry-size must hold seq_length + 1 records")
-                    : "--entry-size must be >= " + std::to_string(c.record_elements() * (c.seq_length + 1)) + " = " +
-                          std::to_string(c.record_elements()) + " * (seq_length + 1) for --learner-arch " + c.arch);
+                    : "--entry-size must be >= " + std::to_string(c.min_entry_size()) + " = " +
+                          c.min_entry_size_formula() + " for --learner-arch " + c.arch +
+                          (c.planes() ? " --atari-records planes" : ""));
         if (c.optimizer != "adam" && c.optimizer != "sgd") throw std::invalid_argument("--optimizer: adam|sgd");
         if (c.publish != "fp32" && c.publish != "bf16") throw std::invalid_argument("--publish: fp32|bf16");
         if (c.data_parallel == 0 || c.batch_size % c.data_parallel != 0)
@@ -148,6 +177,7 @@ struct LearnerConfig {
         c.entry_size = (size_t)program.template get<int>("--entry-size");
         c.seq_length = (size_t)num("--seq-length", str("--seq-length"));
         c.arch = str("--learner-arch");
+        c.atari_records = str("--atari-records");
         c.num_actions = (int)num("--num-actions", str("--num-actions"));
         c.obs_dim = (int)num("--obs-dim", str("--obs-dim"));
         c.hidden = (int)num("--hidden", str("--hidden"));
@@ -202,6 +232,9 @@ void add_learner_arguments(Parser& program) {
     program.add_argument("--seq-length").help("Trajectory length T (entries carry T+1 records)")
         .default_value(std::to_string(d.seq_length));
     program.add_argument("--learner-arch").help("Policy network: mlp | atari").default_value(d.arch);
+    program.add_argument("--atari-records")
+        .help("Atari host records: stacked (84x84x4 per step) | planes (84x84 per step, stack rebuilt on the device)")
+        .default_value(d.atari_records);
     program.add_argument("--num-actions").help("Number of actions A").default_value(std::to_string(d.num_actions));
     program.add_argument("--obs-dim").help("MLP observation width (<= 128)").default_value(std::to_string(d.obs_dim));
     program.add_argument("--hidden").help("MLP hidden width").default_value(std::to_string(d.hidden));
@@ -231,6 +264,12 @@ public:
                 const fi_learner_config k = cfg.abi_config(p, g);
                 if (fi_learner_create(&k, &shards_[p][g]) != FI_OK) {
                     const std::string msg = std::string("fi_learner_create(player ") + std::to_string(p) +
+                                            ", shard " + std::to_string(g) + "): " + fi_last_error();
+                    release();
+                    throw std::runtime_error(msg);
+                }
+                if (cfg.planes() && fi_learner_set_record_format(shards_[p][g], FI_RECORDS_PLANES) != FI_OK) {
+                    const std::string msg = std::string("fi_learner_set_record_format(player ") + std::to_string(p) +
                                             ", shard " + std::to_string(g) + "): " + fi_last_error();
                     release();
                     throw std::runtime_error(msg);

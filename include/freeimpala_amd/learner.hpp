@@ -115,7 +115,7 @@ public:
         lc.players = p;
         lc.batch_size = M;
         lc.entry_size = S;
-        const size_t R = S / lc.record_elements();  // whole records per entry
+        const size_t R = lc.records_in(S);  // whole records per entry (beside the planes' history block)
         if (lc.seq_length + 1 > R) {
             log("warn", "entry size " + std::to_string(S) + " holds at most " + std::to_string(R ? R - 1 : 0) +
                             " steps + bootstrap: seq_length lowered from " + std::to_string(lc.seq_length));

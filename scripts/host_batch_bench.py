@@ -2,12 +2,17 @@
 Learner::trainModel hands over after SharedBuffer::readBatch, data_structures.h:267-300)
 against the step on a batch already resident in HBM (bench.py's `value`).
 
-usage: python scripts/host_batch_bench.py [--arch mlp|atari] [--T 100] [--B 4096] [--steps N]
+usage: python scripts/host_batch_bench.py [--arch mlp|atari] [--records stacked|planes] [--T 100]
+                                          [--B 4096] [--steps N]
 --arch mlp: entries follow the 1 KiB record schema, T+1 records each.
 --arch atari: entries of T+1 Atari records (28 elements = 28,672 B per step: the 84x84x4 frame,
 then the header); at T=100, B=4096 a batch is 12.1 GB and the learner stages it through two
 pinned and two device buffers of that size. When they cannot be allocated the run halves B until
 they can and reports the B it used.
+--arch atari --records planes: entries of T+1 single-plane records (7 elements = 7,168 B per step:
+the newest 84x84 plane, then the header) and the 21-element history block; at T=100, B=4096 a
+batch is 3.05 GB. The planes are channel 3 of the synthetic frames, the history channels 0..2 of
+frame 0, and episode_start follows every discount of 0.
 Prints one JSON line:
   resident    env-steps/s of fi_learner_step_resident
   host_serial        fi_learner_step: pinned staging copy + one H2D + ingest + step, returns
@@ -21,6 +26,7 @@ Prints one JSON line:
   ingest             (from set_profiling) the "ingest" phase of a host-fed step -- it starts
                      with the wait for the batch's H2D -- and the ingest kernels alone; for
                      atari also the copy floor 2 * (T+1) * B * 28,224 B / 6.3 TB/s and the gap
+                     (planes: the floor reads (T+1+3) * B * 7,056 B and writes (T+1) * B * 28,224 B)
 """
 import argparse
 import ctypes as C
@@ -50,13 +56,13 @@ def kernel_times(L):
     return {names[i]: ms[i] for i in range(n)}
 
 
-def make_learner(arch, T, B, A):
+def make_learner(arch, T, B, A, records="stacked"):
     """The learner with its host staging allocated, at the largest power-of-two B <= the asked
     one whose staging buffers can be had."""
     from freeimpala_amd._abi import FiError
     from freeimpala_amd.learner import DeviceLearner
     while True:
-        L = DeviceLearner(arch, seq_len=T, batch=B, num_actions=A, optimizer="adam")
+        L = DeviceLearner(arch, seq_len=T, batch=B, num_actions=A, optimizer="adam", records=records)
         try:
             L.acquire_staging()  # allocates the two pinned and the two device buffers
             return L, B
@@ -71,23 +77,34 @@ def make_learner(arch, T, B, A):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", choices=("mlp", "atari"), default="mlp")
+    ap.add_argument("--records", choices=("stacked", "planes"), default="stacked", help="atari host record format")
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=None, help="timed steps per row (default 8; atari 4)")
     args = ap.parse_args()
-    from freeimpala_amd.learner import HostBatch, pack_atari_records, pack_records
+    from freeimpala_amd.learner import HostBatch, pack_atari_plane_records, pack_atari_records, pack_records
     atari = args.arch == "atari"
+    planes = args.records == "planes"
+    if planes and not atari:
+        ap.error("--records planes needs --arch atari")
     T, A = args.T, 18
     steps = args.steps or (4 if atari else 8)
-    L, B = make_learner(args.arch, T, args.B, A)
-    log(f"{args.arch} T={T} B={B}: staging 2 x {B * L.entry_bytes / 1e9:.2f} GB pinned + device")
+    L, B = make_learner(args.arch, T, args.B, A, args.records)
+    log(f"{args.arch} {args.records if atari else ''} T={T} B={B}: staging 2 x {B * L.entry_bytes / 1e9:.2f} GB pinned + device")
     L.synth(seed=42)
     mu = L.tensor("mu", shape=(T, B, A))
     act = L.tensor("actions", np.int32, (T, B))
     rew = L.tensor("rewards", shape=(T, B))
     disc = L.tensor("discounts", shape=(T, B))
     t0 = time.perf_counter()
-    if atari:
+    if planes:
+        obs = L.tensor("frames", np.uint8, (T + 1, B, 84, 84, 4))
+        start = np.zeros((T + 1, B), bool)
+        start[1:] = disc == 0
+        entries = HostBatch(pack_atari_plane_records(
+            np.ascontiguousarray(obs[..., 3]), np.ascontiguousarray(obs[0, :, :, :, :3].transpose(3, 0, 1, 2)),
+            start, mu, act, rew, disc))
+    elif atari:
         obs = L.tensor("frames", np.uint8, (T + 1, B, 84, 84, 4))
         entries = HostBatch(pack_atari_records(obs, mu, act, rew, disc))
     else:
@@ -147,12 +164,13 @@ def main():
     ingest = {"phase_ms": round(L.phase_times()["ingest"], 3), "kernels_ms": round(kernel_times(L).get("ingest", 0.0), 3)}
     L.set_profiling(False)
     if atari:
-        floor_ms = 1e3 * 2 * (T + 1) * B * 28224 / HBM_ACHIEVABLE
+        moved = ((T + 4) * 7056 + (T + 1) * 28224) * B if planes else 2 * (T + 1) * B * 28224
+        floor_ms = 1e3 * moved / HBM_ACHIEVABLE
         ingest["copy_floor_ms"] = round(floor_ms, 3)
         ingest["kernels_over_floor"] = round(ingest["kernels_ms"] / floor_ms, 2)
     mb = B * eb / 1e6
     out = {
-        "arch": args.arch, "T": T, "B": B, "B_requested": args.B, "entry_bytes": eb, "batch_mb": round(mb, 1),
+        "arch": args.arch, **({"records": args.records} if atari else {}), "T": T, "B": B, "B_requested": args.B, "entry_bytes": eb, "batch_mb": round(mb, 1),
         "resident": {"ms_per_step": round(1e3 * res, 3), "env_steps_per_s": round(T * B / res, 1)},
         "host_serial": {"ms_per_step": round(1e3 * ser, 3), "env_steps_per_s": round(T * B / ser, 1)},
         "host_async": {"ms_per_step": round(1e3 * asy, 3), "env_steps_per_s": round(T * B / asy, 1),

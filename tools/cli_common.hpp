@@ -167,7 +167,7 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
         if (!program.is_used("--seq-length")) {  // default T: what an entry / a game holds
             const size_t per_player = (P.game_steps + P.num_players - 1) / std::max<size_t>(1, P.num_players);
             lc.seq_length = std::max<size_t>(
-                1, std::min<size_t>({lc.seq_length, P.entry_size / lc.record_elements(), per_player}) - 1);
+                1, std::min<size_t>({lc.seq_length, lc.records_in(P.entry_size), per_player}) - 1);
         }
     } catch (const std::exception& e) {
         const std::string msg = e.what();
@@ -186,20 +186,21 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
         std::cerr << "Game steps must be less than or equal to entry size\n";
         return 1;
     }
-    // records of more than one element (Atari: 28): each player's share of the game must fit its
-    // entry, and an explicit --seq-length is not lowered to what the entry holds but refused
-    const size_t rec = lc.record_elements();
+    // records of more than one element (Atari: 28, or 7 and a 21-element history block with
+    // --atari-records planes): each player's share of the game must fit its entry, and an explicit
+    // --seq-length is not lowered to what the entry holds but refused
+    const size_t rec = lc.record_elements(), tail = lc.entry_tail_elements();
     if (rec > 1) {
-        if (P.entry_size < rec * (lc.seq_length + 1)) {
-            std::cerr << "--entry-size must be >= " << rec * (lc.seq_length + 1) << " = " << rec
-                      << " * (seq_length + 1) elements for --learner-arch " << lc.arch << "\n";
+        if (P.entry_size < lc.min_entry_size()) {
+            std::cerr << "--entry-size must be >= " << lc.min_entry_size() << " = " << lc.min_entry_size_formula()
+                      << " elements for --learner-arch " << lc.arch << (tail ? " --atari-records planes" : "") << "\n";
             return 1;
         }
         const size_t per_player = (P.game_steps + P.num_players - 1) / P.num_players;
-        if (per_player * rec > P.entry_size) {
-            std::cerr << "Each player's " << per_player << " game steps need " << per_player * rec
-                      << " elements (" << rec << " per record): raise --entry-size (" << P.entry_size
-                      << ") or lower --game-steps\n";
+        if (per_player * rec + tail > P.entry_size) {
+            std::cerr << "Each player's " << per_player << " game steps need " << per_player * rec + tail
+                      << " elements (" << rec << " per record" << (tail ? ", " + std::to_string(tail) + " of history" : "")
+                      << "): raise --entry-size (" << P.entry_size << ") or lower --game-steps\n";
             return 1;
         }
     }
@@ -214,7 +215,9 @@ inline int parse(ArgumentParser& program, int argc, char** argv, Params& P, Lear
 
 // One synthetic actor's game (agent.h:34-73 with the learner's record schema instead of
 // rand() bytes): step s goes to player s % P at byte (s / P) * 1024 of that player's entry
-// (MLP), or (s / P) * 28 * 1024 with the Atari record.
+// (MLP), or (s / P) * 28 * 1024 with the Atari record, (s / P) * 7 * 1024 with its plane record.
+// A plane entry keeps seq_length + 1 records (the history block follows them, so later steps of
+// the game are dropped) and ends with three random history planes.
 class GameWriter {
 public:
     GameWriter(size_t actor_id, const Params& P, const LearnerConfig& lc)
@@ -226,12 +229,73 @@ public:
         const size_t entry_bytes = P_.entry_size * ELEMENT_SIZE;
         for (auto& e : entries_) std::fill(e.begin(), e.end(), 0);
         const size_t rec_bytes = lc_.record_elements() * ELEMENT_SIZE;
+        if (lc_.planes()) return play_planes(versions, rec_bytes);
         for (size_t s = 0; s < P_.game_steps; ++s) {
             const size_t p = s % P_.num_players;
             const size_t off = (s / P_.num_players) * rec_bytes;
             if (off + rec_bytes <= entry_bytes) write_record(entries_[p].data() + off, (uint32_t)versions[p]);
         }
         return entries_;
+    }
+
+private:
+    static constexpr size_t kPlane = 84 * 84;
+
+    void random_bytes(char* r, size_t n) {  // n: a multiple of 8
+        for (size_t i = 0; i < n; i += 8) {
+            const uint64_t w = rng_();
+            std::memcpy(r + i, &w, 8);
+        }
+    }
+
+    // Plane records: the stack restarts (episode_start) on the record after
+    // one with discount 0, and on record 0 with a small probability (the previous entry's last
+    // step ended the episode).
+    std::vector<std::vector<char>>& play_planes(const std::vector<uint64_t>& versions, size_t rec_bytes) {
+        std::uniform_real_distribution<float> uni(0.f, 1.f);
+        const size_t hist_off = (lc_.seq_length + 1) * rec_bytes;
+        std::vector<char> ended(P_.num_players, 0);
+        for (size_t s = 0; s < P_.game_steps; ++s) {
+            const size_t p = s % P_.num_players, k = s / P_.num_players;
+            if (k > lc_.seq_length) continue;
+            char* r = entries_[p].data() + k * rec_bytes;
+            const uint32_t start = k == 0 ? (uni(rng_) < 0.05f ? 1u : 0u) : (uint32_t)ended[p];
+            ended[p] = write_plane_record(r, (uint32_t)versions[p], start) == 0.f;
+        }
+        for (auto& e : entries_) random_bytes(e.data() + hist_off, 3 * kPlane);
+        return entries_;
+    }
+
+    // plane [0, 7056) | mu[18] 7056 | action 7128 | reward 7132 | discount 7136 | flags 7140 |
+    // episode_start 7144; returns the discount
+    float write_plane_record(char* r, uint32_t version, uint32_t start) {
+        std::normal_distribution<float> nrm(0.f, 1.f);
+        std::uniform_real_distribution<float> uni(0.f, 1.f);
+        random_bytes(r, kPlane);
+        r += kPlane;
+        float mu[18] = {};
+        const int A = lc_.num_actions;
+        double mx = -1e30, z = 0.0;
+        for (int a = 0; a < A; ++a) mx = std::max(mx, (double)(mu[a] = nrm(rng_)));
+        for (int a = 0; a < A; ++a) z += std::exp(mu[a] - mx);
+        double u = uni(rng_) * z, c = 0.0;
+        int32_t action = A - 1;
+        for (int a = 0; a < A; ++a) {
+            c += std::exp(mu[a] - mx);
+            if (u < c) {
+                action = a;
+                break;
+            }
+        }
+        const float reward = (float)((int)(rng_() % 3) - 1);
+        const float discount = uni(rng_) < 0.01f ? 0.f : lc_.gamma;
+        std::memcpy(r, mu, sizeof mu);
+        std::memcpy(r + 72, &action, 4);
+        std::memcpy(r + 76, &reward, 4);
+        std::memcpy(r + 80, &discount, 4);
+        std::memcpy(r + 84, &version, 4);
+        std::memcpy(r + 88, &start, 4);
+        return discount;
     }
 
 private:
