@@ -1,0 +1,197 @@
+"""Host side of batched policy inference with action sampling (include/fi_actor.h).
+
+An ``Actor`` evaluates the policy a learner publishes on ``num_envs`` environments per call and
+draws their actions on the device:
+
+  a = Actor("atari", num_envs=256, num_actions=6)
+  a.set_params(blob, version)                 # the bytes of DeviceLearner.get_blob() / get_params()
+  out = a.act_planes(planes, episode_start)   # dict(actions (N,), logits (N, A), values (N,))
+
+The logits returned are the policy's own: they are what an actor writes into a record's mu field.
+An Atari handle keeps every environment's 4-frame stack on the device (``act_planes`` sends one
+84x84 plane per environment; ``stacks()`` reads them back); ``act_frames`` takes whole stacks.
+Everything runs in HIP kernels of libfi_learner.so; there is no CPU path."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import check
+
+FI_ACT_SAMPLE, FI_ACT_GREEDY = 0, 1
+MODES = {"sample": FI_ACT_SAMPLE, "greedy": FI_ACT_GREEDY}
+PHASES = ["h2d", "push", "forward", "sample", "d2h"]
+PLANE_BYTES = 84 * 84
+STACK_BYTES = 4 * PLANE_BYTES
+
+
+class ActorConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("arch", C.c_int32), ("num_envs", C.c_int32),
+                ("num_actions", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32),
+                ("device", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint64)]
+
+
+_P = C.c_void_p
+SIGNATURES = {  # every symbol include/fi_actor.h declares
+    "fi_actor_config_init": ([C.POINTER(ActorConfig)], None),
+    "fi_actor_create": ([C.POINTER(ActorConfig), C.POINTER(_P)], C.c_int),
+    "fi_actor_destroy": ([_P], None),
+    "fi_actor_param_count": ([_P], C.c_size_t),
+    "fi_actor_set_params": ([_P, _P, C.c_size_t, C.c_uint64], C.c_int),
+    "fi_actor_version": ([_P], C.c_uint64),
+    "fi_actor_set_mode": ([_P, C.c_int], C.c_int),
+    "fi_actor_seed": ([_P, C.c_uint64, C.c_uint64], C.c_int),
+    "fi_actor_act_obs": ([_P, _P, _P, _P, _P], C.c_int),
+    "fi_actor_act_frames": ([_P, _P, _P, _P, _P], C.c_int),
+    "fi_actor_act_planes": ([_P, _P, _P, _P, _P, _P], C.c_int),
+    "fi_actor_reset_stacks": ([_P], C.c_int),
+    "fi_actor_read_stacks": ([_P, _P, C.c_size_t], C.c_int),
+    "fi_actor_set_profiling": ([_P, C.c_int], C.c_int),
+    "fi_actor_phase_times": ([_P, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "fi_push_planes": ([_P, _P, _P, C.c_int, _P], C.c_int),
+    "fi_sample_actions": ([_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P], C.c_int),
+}
+_bound = None
+
+
+def lib():
+    global _bound
+    L = _abi.lib()
+    if _bound is not L:
+        for name, (args, res) in SIGNATURES.items():
+            f = getattr(L, name)
+            f.argtypes = args
+            f.restype = res
+        _bound = L
+    return L
+
+
+def _mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in MODES:
+            raise ValueError(f"mode: sample | greedy, not {mode!r}")
+        return MODES[mode]
+    return int(mode)
+
+
+class Actor:
+    def __init__(self, arch: str = "mlp", num_envs: int = 1, num_actions: int = 18, obs_dim: int = 128,
+                 hidden: int = 256, mode: str = "sample", seed: int = 0, device: int = 0):
+        if arch not in ("mlp", "atari"):
+            raise ValueError(f"arch: mlp | atari, not {arch!r}")
+        cfg = ActorConfig()
+        lib().fi_actor_config_init(C.byref(cfg))
+        cfg.arch = _abi.FI_ARCH_MLP if arch == "mlp" else _abi.FI_ARCH_ATARI
+        cfg.num_envs, cfg.num_actions, cfg.obs_dim, cfg.hidden = num_envs, num_actions, obs_dim, hidden
+        cfg.device, cfg.mode, cfg.seed = device, _mode(mode), seed
+        self._h = _P()
+        check(lib().fi_actor_create(C.byref(cfg), C.byref(self._h)), "fi_actor_create")
+        self.arch, self.N, self.A, self.D, self.H = arch, num_envs, num_actions, obs_dim, hidden
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().fi_actor_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # --- parameters
+    @property
+    def param_count(self) -> int:
+        return int(lib().fi_actor_param_count(self._h))
+
+    def set_params(self, p: np.ndarray | bytes, version: int = 0) -> None:
+        """The published blob (bytes: fp32 or bf16) or an fp32 array of param_count values."""
+        a = np.frombuffer(p, np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p)
+        check(lib().fi_actor_set_params(self._h, a.ctypes.data, a.nbytes, version), "fi_actor_set_params")
+
+    @property
+    def version(self) -> int:
+        return int(lib().fi_actor_version(self._h))
+
+    def set_mode(self, mode) -> None:
+        check(lib().fi_actor_set_mode(self._h, _mode(mode)), "fi_actor_set_mode")
+
+    def seed(self, seed: int, draw: int = 0) -> None:
+        """Key of the action draws and the index the next act call uses."""
+        check(lib().fi_actor_seed(self._h, seed, draw), "fi_actor_seed")
+
+    # --- acting
+    def _outputs(self):
+        return (np.empty(self.N, np.int32), np.empty((self.N, self.A), np.float32), np.empty(self.N, np.float32))
+
+    def _input(self, a, dtype, shape, what):
+        a = np.ascontiguousarray(a, dtype)
+        if a.size != int(np.prod(shape)):
+            raise ValueError(f"{what}: {a.shape} does not hold {shape}")
+        return a
+
+    def _finish(self, rc, what, out):
+        """A call that reports NaN / Inf rows has still filled its outputs: they ride on the error."""
+        try:
+            check(rc, what)
+        except _abi.FiError as e:
+            e.outputs = out
+            raise
+        return out
+
+    def act_obs(self, obs) -> dict:
+        obs = self._input(obs, np.float32, (self.N, self.D), "obs")
+        act, log, val = self._outputs()
+        rc = lib().fi_actor_act_obs(self._h, obs.ctypes.data, act.ctypes.data, log.ctypes.data, val.ctypes.data)
+        return self._finish(rc, "fi_actor_act_obs", dict(actions=act, logits=log, values=val))
+
+    def act_frames(self, frames) -> dict:
+        frames = self._input(frames, np.uint8, (self.N, 84, 84, 4), "frames")
+        act, log, val = self._outputs()
+        rc = lib().fi_actor_act_frames(self._h, frames.ctypes.data, act.ctypes.data, log.ctypes.data,
+                                       val.ctypes.data)
+        return self._finish(rc, "fi_actor_act_frames", dict(actions=act, logits=log, values=val))
+
+    def act_planes(self, planes, episode_start) -> dict:
+        planes = self._input(planes, np.uint8, (self.N, 84, 84), "planes")
+        start = self._input(np.asarray(episode_start) != 0, np.uint8, (self.N,), "episode_start")
+        act, log, val = self._outputs()
+        rc = lib().fi_actor_act_planes(self._h, planes.ctypes.data, start.ctypes.data, act.ctypes.data,
+                                       log.ctypes.data, val.ctypes.data)
+        return self._finish(rc, "fi_actor_act_planes", dict(actions=act, logits=log, values=val))
+
+    def reset_stacks(self) -> None:
+        check(lib().fi_actor_reset_stacks(self._h), "fi_actor_reset_stacks")
+
+    def stacks(self) -> np.ndarray:
+        """The stacks the last act_planes ran the policy on: (N, 84, 84, 4) uint8."""
+        out = np.empty((self.N, 84, 84, 4), np.uint8)
+        check(lib().fi_actor_read_stacks(self._h, out.ctypes.data, out.nbytes), "fi_actor_read_stacks")
+        return out
+
+    # --- profiling
+    def set_profiling(self, on: bool) -> None:
+        check(lib().fi_actor_set_profiling(self._h, int(on)), "fi_actor_set_profiling")
+
+    def phase_times(self) -> dict:
+        """Mean device ms per act call since profiling was switched on (or last read), by phase."""
+        ms = (C.c_float * len(PHASES))()
+        n = C.c_int(0)
+        check(lib().fi_actor_phase_times(self._h, ms, len(PHASES), C.byref(n)), "fi_actor_phase_times")
+        d = dict(zip(PHASES, [float(x) for x in ms]))
+        d["calls"] = n.value
+        return d
+
+
+def push_planes(stacks_ptr: int, planes_ptr: int, start_ptr: int, n: int, stream=None) -> None:
+    """fi_push_planes on device pointers."""
+    check(lib().fi_push_planes(stacks_ptr, planes_ptr, start_ptr, n, stream), "fi_push_planes")
+
+
+def sample_actions(logits_ptr: int, n: int, a: int, mode, seed: int, draw: int, actions_ptr: int,
+                   nonfinite_ptr: int | None = None, stream=None) -> None:
+    """fi_sample_actions on device pointers."""
+    check(lib().fi_sample_actions(logits_ptr, n, a, _mode(mode), seed, draw, actions_ptr, nonfinite_ptr, stream),
+          "fi_sample_actions")

@@ -1,0 +1,561 @@
+// actor.hip -- fi_actor: batched policy inference with action sampling, behind the C ABI of
+// include/fi_actor.h. The other side of the loop the learner closes: N environments' observations
+// in, the published policy's logits / values and one drawn action per environment out.
+//
+//   * push_planes_kernel: the per-environment 4-frame stacks (N, 84, 84, 4) u8 live in device
+//     memory; a step sends one 84x84 plane per environment and the kernel slides it in
+//   * the forward is the learner's own (atari_forward on N frames; f32_linear_fwd x2 +
+//     f32_heads_fwd on N rows), unchanged, so a row's logits are the bits the learner computes
+//   * sample_actions_kernel: one categorical draw (or the argmax) per row, a counter-based rule a
+//     host reference reproduces (fi_actor.h)
+// One HIP stream per handle, no global mutable state, no HIP graphs.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "atari.h"
+#include "fi_actor.h"
+#include "fi_common.h"
+#include "kernels.h"
+
+namespace fi {
+
+// ---------------------------------------------------------------- stack push
+// stacks[i] (84, 84, 4) u8 <- planes[i] (84, 84) u8, in place. A pixel is one dword of the stack
+// (byte c = channel c) and one byte p of the plane: the new dword is (w >> 8) | (p << 24) on a
+// shift and p * 0x01010101 on an episode start, one v_perm_b32 either way (interleave4's idiom,
+// misc.hip).
+//   A one-wave workgroup owns an environment i and a run of 64 16-byte plane pieces (1,024
+// pixels = 256 16-byte stack pieces). Lane j loads plane piece 64 run + j; the wave turns the 256
+// plane dwords through LDS so that lane j holds dwords 64k + j (k = 0..3), the four pixels of
+// stack piece 64k + j of the run. Every 16-byte load and store is then contiguous over the wave
+// (1 KiB). The start flag is uniform per workgroup: one scalar load of the aligned dword that
+// holds byte i (gfx950 has no scalar byte load; the dword holds a valid byte, so it lies in the
+// array's own page) and a uniform branch -- a start does not read the stack. 7 runs cover the 441
+// plane pieces: the last has 57, and 228 = 3 * 64 + 36 stack pieces (the tail lanes are skipped).
+// 7 N workgroups, no grid cap. HBM traffic: (2 * 28,224 + 7,056) N bytes (a start: 28,224 fewer).
+constexpr int kPlaneBytes = 84 * 84;
+constexpr int kPlanePieces = kPlaneBytes / 16;        // 441
+constexpr int kPlaneRuns = (kPlanePieces + 63) / 64;  // 7
+constexpr int kStackBytes = 4 * kPlaneBytes;
+constexpr int kStackPieces = kStackBytes / 16;        // 1,764
+static_assert(kPlanePieces * 16 == kPlaneBytes && kStackPieces == 4 * kPlanePieces, "whole 16-byte pieces");
+static_assert((size_t)kStackBytes == AtariNet::kFrameBytes, "a stack is one frame of the policy");
+
+// pixel q of plane dword n into the top byte of stack dword w, the rest one channel down
+template <int Q>
+__device__ __forceinline__ uint32_t shift_in(uint32_t w, uint32_t n) {
+    return __builtin_amdgcn_perm(n, w, ((uint32_t)(4 + Q) << 24) | 0x00030201u);
+}
+template <int Q>
+__device__ __forceinline__ uint32_t fill4(uint32_t n) {
+    return __builtin_amdgcn_perm(n, n, (uint32_t)Q * 0x01010101u);
+}
+
+__global__ __launch_bounds__(64) void push_planes_kernel(uint4* __restrict__ stacks, const uint4* __restrict__ planes,
+                                                         const uint8_t* __restrict__ start) {
+    __shared__ uint4 turn[64];
+    const int lane = threadIdx.x & 63;
+    const int env = blockIdx.x / kPlaneRuns, run = blockIdx.x - env * kPlaneRuns;
+    const int piece = run * 64 + lane;
+    uint4 p = make_uint4(0u, 0u, 0u, 0u);
+    if (piece < kPlanePieces) p = planes[(size_t)env * kPlanePieces + piece];
+    const uint8_t* __restrict__ fp = start + env;
+    const uint32_t fsh = (uint32_t)((uintptr_t)fp & 3u);
+    const uint32_t fword = *(const uint32_t*)(fp - fsh);
+    const bool first = ((fword >> (8u * fsh)) & 0xffu) != 0u;
+    uint4* __restrict__ st = stacks + (size_t)env * kStackPieces + run * 256 + lane;
+    const int left = kStackPieces - run * 256 - lane;  // stack pieces from this lane's first to the end
+    uint4 w[4];
+    if (!first) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (64 * k < left) w[k] = st[64 * k];
+    }
+    turn[lane] = p;
+    __syncthreads();
+    const uint32_t* xd = (const uint32_t*)turn;
+    uint32_t n[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) n[k] = xd[64 * k + lane];
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (64 * k < left) st[64 * k] = make_uint4(fill4<0>(n[k]), fill4<1>(n[k]), fill4<2>(n[k]), fill4<3>(n[k]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (64 * k < left)
+                st[64 * k] = make_uint4(shift_in<0>(w[k].x, n[k]), shift_in<1>(w[k].y, n[k]),
+                                        shift_in<2>(w[k].z, n[k]), shift_in<3>(w[k].w, n[k]));
+    }
+}
+
+static int push_planes_launch(uint8_t* stacks, const uint8_t* planes, const uint8_t* start, int N, hipStream_t s) {
+    FI_REQUIRE(stacks && planes && start, "push_planes: null argument");
+    FI_REQUIRE(N >= 1, "push_planes: N must be >= 1");
+    FI_REQUIRE(N <= 0x7fffffff / kPlaneRuns, "push_planes: too many environments");
+    FI_REQUIRE((uintptr_t)stacks % 16 == 0 && (uintptr_t)planes % 16 == 0,
+               "push_planes: stacks and planes must be 16-byte aligned");
+    hipLaunchKernelGGL(push_planes_kernel, dim3((unsigned)(N * kPlaneRuns)), dim3(64), 0, s, (uint4*)stacks,
+                       (const uint4*)planes, start);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+// ---------------------------------------------------------------- sampling
+// One lane per row, the row (A <= AMAX floats) in registers. The sums run a = 0..A-1 ascending in
+// fp32, exactly as fi_actor.h states the rule, so a host reference lands on the same action except
+// where u Z falls within rounding of a running sum.
+template <int AMAX>
+__global__ __launch_bounds__(256) void sample_actions_kernel(const float* __restrict__ logits, int N, int A, int mode,
+                                                             uint64_t seed, uint64_t draw, int32_t* __restrict__ actions,
+                                                             int* __restrict__ nonfinite) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float* __restrict__ row = logits + (size_t)i * A;
+    float l[AMAX];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) l[a] = a < A ? row[a] : 0.f;
+    float m = l[0];
+    int am = 0;
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (a < A) {
+            finite = finite && (fabsf(l[a]) <= 3.402823466e+38f);  // false for NaN and for +-Inf
+            if (l[a] > m) {
+                m = l[a];
+                am = a;
+            }
+        }
+    int act = 0;
+    if (!finite) {
+        if (nonfinite) atomicAdd(nonfinite, 1);
+    } else if (mode == FI_ACT_GREEDY) {
+        act = am;
+    } else {
+        float Z = 0.f;
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a)
+            if (a < A) {
+                l[a] = expf(l[a] - m);
+                Z += l[a];
+            }
+        const uint4 x = philox4(seed, draw * (uint64_t)N + (uint64_t)i, ST_SAMPLE);
+        const float u = (float)(x.x >> 8) * 0x1p-24f;
+        const float thr = u * Z;
+        float c = 0.f;
+        bool found = false;
+        act = A - 1;
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a)
+            if (a < A) {
+                c += l[a];
+                if (!found && c > thr) {
+                    act = a;
+                    found = true;
+                }
+            }
+    }
+    actions[i] = act;
+}
+
+static int sample_actions_launch(const float* logits, int N, int A, int mode, uint64_t seed, uint64_t draw,
+                                 int32_t* actions, int* nonfinite, hipStream_t s) {
+    FI_REQUIRE(logits && actions, "sample_actions: null argument");
+    FI_REQUIRE(N >= 1, "sample_actions: N must be >= 1");
+    FI_REQUIRE(A >= 2 && A <= 64, "sample_actions: 2 <= A <= 64");
+    FI_REQUIRE(mode == FI_ACT_SAMPLE || mode == FI_ACT_GREEDY, "sample_actions: unknown mode");
+    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+#define FI_SAMPLE(M) \
+    hipLaunchKernelGGL(sample_actions_kernel<M>, grid, block, 0, s, logits, N, A, mode, seed, draw, actions, nonfinite)
+    if (A <= 8) FI_SAMPLE(8);
+    else if (A <= 18) FI_SAMPLE(18);
+    else if (A <= 32) FI_SAMPLE(32);
+    else FI_SAMPLE(64);
+#undef FI_SAMPLE
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+}  // namespace fi
+
+using namespace fi;
+
+// ------------------------------------------------------------------ the handle
+namespace {
+enum { PH_H2D = 0, PH_PUSH, PH_FWD, PH_SAMPLE, PH_D2H, PH_COUNT };
+enum { IN_OBS = 0, IN_FRAMES, IN_PLANES };
+constexpr size_t kAlign = 256;
+size_t round_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+}  // namespace
+
+struct fi_actor {
+    fi_actor_config cfg{};
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    int N = 0, A = 0, D = 0, H = 0;
+    size_t nparams = 0;
+    float* params = nullptr;
+    bool have_params = false;
+    uint64_t version = 0;
+    int mode = FI_ACT_SAMPLE;
+    uint64_t seed = 0, draw = 0;
+    // inputs on the device
+    float* obs = nullptr;        // MLP (N, D)
+    uint8_t* frames = nullptr;   // Atari: act_frames' input (N, 84, 84, 4)
+    uint8_t* stacks = nullptr;   // Atari: the environments' stacks, pushed by act_planes
+    uint8_t* planes = nullptr;   // Atari: (N, 7056) then the N start flags
+    AtariNet* atari = nullptr;
+    float* h1 = nullptr;  // MLP
+    float* h2 = nullptr;
+    // outputs, one device block and one D2H copy: actions | values | logits | non-finite row count
+    char* out = nullptr;
+    size_t off_val = 0, off_log = 0, off_bad = 0, out_bytes = 0;
+    char* pin_in = nullptr;
+    size_t pin_in_bytes = 0;
+    char* pin_out = nullptr;
+    bool profiling = false;
+    hipEvent_t ev[PH_COUNT + 1] = {};
+    double phase_sum[PH_COUNT] = {};
+    int phase_calls = 0;
+    std::vector<void*> allocs;
+};
+
+static int dalloc(fi_actor* a, void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) {
+        *p = nullptr;
+        return fail(FI_ERR_OOM, std::string("actor: hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+    }
+    a->allocs.push_back(*p);
+    return FI_OK;
+}
+
+static void destroy(fi_actor* a) {
+    if (!a) return;
+    if (a->stream) (void)hipStreamSynchronize(a->stream);
+    atari_destroy(a->atari);
+    for (void* p : a->allocs) (void)hipFree(p);
+    if (a->pin_in) (void)hipHostFree(a->pin_in);
+    if (a->pin_out) (void)hipHostFree(a->pin_out);
+    for (auto& e : a->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (a->stream) (void)hipStreamDestroy(a->stream);
+    delete a;
+}
+
+extern "C" void fi_actor_config_init(fi_actor_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->struct_size = sizeof(*c);
+    c->arch = FI_ARCH_MLP;
+    c->num_envs = 1;
+    c->num_actions = 18;
+    c->obs_dim = 128;
+    c->hidden = 256;
+    c->device = 0;
+    c->mode = FI_ACT_SAMPLE;
+    c->seed = 0;
+}
+
+static int create(const fi_actor_config* cfg, fi_actor** out) {
+    FI_REQUIRE(cfg && out, "actor_create: null argument");
+    *out = nullptr;
+    FI_REQUIRE(cfg->struct_size == sizeof(fi_actor_config), "actor_create: struct_size mismatch");
+    FI_REQUIRE(cfg->arch == FI_ARCH_MLP || cfg->arch == FI_ARCH_ATARI, "actor_create: unknown arch");
+    FI_REQUIRE(cfg->num_envs >= 1, "actor_create: num_envs must be >= 1");
+    FI_REQUIRE(cfg->mode == FI_ACT_SAMPLE || cfg->mode == FI_ACT_GREEDY, "actor_create: unknown mode");
+    if (cfg->arch == FI_ARCH_MLP) {
+        FI_REQUIRE(cfg->num_actions >= 2 && cfg->num_actions <= 64, "actor_create: 2 <= A <= 64");
+        FI_REQUIRE(cfg->obs_dim >= 1 && cfg->obs_dim <= 128 && cfg->hidden >= 1 && cfg->hidden <= 4096,
+                   "actor_create: MLP needs 1 <= obs_dim <= 128 (record schema), hidden <= 4096");
+    } else {
+        FI_REQUIRE(cfg->num_actions >= 2 && cfg->num_actions <= 18,
+                   "actor_create: the Atari policy needs 2 <= A <= 18 (the full ALE action set is 18)");
+    }
+    int ndev = 0;
+    FI_HIP_CHECK(hipGetDeviceCount(&ndev));
+    FI_REQUIRE(cfg->device >= 0 && cfg->device < ndev, "actor_create: no such HIP device");
+    FI_HIP_CHECK(hipSetDevice(cfg->device));
+
+    fi_actor* a = new (std::nothrow) fi_actor();
+    FI_REQUIRE(a, "actor_create: out of host memory");
+    struct Guard {
+        fi_actor* a;
+        bool ok = false;
+        ~Guard() { if (!ok) destroy(a); }
+    } guard{a};
+    a->cfg = *cfg;
+    a->dev = cfg->device;
+    a->N = cfg->num_envs;
+    a->A = cfg->num_actions;
+    a->D = cfg->obs_dim;
+    a->H = cfg->hidden;
+    a->mode = cfg->mode;
+    a->seed = cfg->seed;
+    FI_HIP_CHECK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+    for (auto& e : a->ev) FI_HIP_CHECK(hipEventCreate(&e));
+
+    const size_t N = a->N, A = a->A;
+    if (cfg->arch == FI_ARCH_MLP) {
+        const size_t D = a->D, H = a->H, O = A + 1;
+        a->nparams = D * H + H + H * H + H + H * O + O;
+        FI_TRY(dalloc(a, (void**)&a->obs, N * D * sizeof(float)));
+        FI_TRY(dalloc(a, (void**)&a->h1, N * H * sizeof(float)));
+        FI_TRY(dalloc(a, (void**)&a->h2, N * H * sizeof(float)));
+        a->pin_in_bytes = N * D * sizeof(float);
+    } else {
+        // B = N, T = 0: N frames. The net's backward buffers come with it
+        a->atari = atari_create(a->N, 0, a->A);
+        FI_REQUIRE(a->atari, "actor_create: Atari net allocation failed: " + std::string(fi_last_error()));
+        a->nparams = atari_param_count(a->A);
+        FI_TRY(dalloc(a, (void**)&a->frames, N * kStackBytes));
+        FI_TRY(dalloc(a, (void**)&a->stacks, N * kStackBytes));
+        FI_TRY(dalloc(a, (void**)&a->planes, N * kPlaneBytes + round_up(N)));
+        FI_HIP_CHECK(hipMemsetAsync(a->stacks, 0, N * kStackBytes, a->stream));
+        a->pin_in_bytes = N * kStackBytes;
+    }
+    FI_TRY(dalloc(a, (void**)&a->params, a->nparams * sizeof(float)));
+    a->off_val = round_up(N * sizeof(int32_t));
+    a->off_log = a->off_val + round_up(N * sizeof(float));
+    a->off_bad = a->off_log + round_up(N * A * sizeof(float));
+    a->out_bytes = a->off_bad + sizeof(int);
+    FI_TRY(dalloc(a, (void**)&a->out, a->out_bytes));
+    FI_HIP_CHECK(hipMemsetAsync(a->out, 0, a->out_bytes, a->stream));
+    for (char** p : {&a->pin_in, &a->pin_out}) {
+        const size_t bytes = p == &a->pin_in ? a->pin_in_bytes : a->out_bytes;
+        const hipError_t e = hipHostMalloc((void**)p, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();
+            return fail(FI_ERR_OOM, "actor_create: hipHostMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
+        }
+    }
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    guard.ok = true;
+    *out = a;
+    return FI_OK;
+}
+
+extern "C" int fi_actor_create(const fi_actor_config* cfg, fi_actor** out) {
+    try {
+        return create(cfg, out);
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_OOM, std::string("actor_create: ") + e.what());
+    }
+}
+
+extern "C" void fi_actor_destroy(fi_actor* a) {
+    if (!a) return;
+    (void)hipSetDevice(a->dev);
+    destroy(a);
+}
+
+extern "C" size_t fi_actor_param_count(const fi_actor* a) { return a ? a->nparams : 0; }
+extern "C" uint64_t fi_actor_version(const fi_actor* a) { return a ? a->version : 0; }
+
+static int set_params(fi_actor* a, const void* src, size_t bytes, uint64_t version) {
+    FI_REQUIRE(a && src, "actor_set_params: null argument");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    std::vector<float> tmp;
+    const float* p;
+    if (bytes == a->nparams * 4) {
+        p = (const float*)src;
+    } else if (bytes == a->nparams * 2) {  // bf16 -> fp32: the low 16 bits are zero
+        tmp.resize(a->nparams);
+        const uint16_t* s = (const uint16_t*)src;
+        for (size_t i = 0; i < a->nparams; ++i) {
+            const uint32_t u = (uint32_t)s[i] << 16;
+            std::memcpy(&tmp[i], &u, 4);
+        }
+        p = tmp.data();
+    } else {
+        return fail(FI_ERR_INVALID, "actor_set_params: " + std::to_string(bytes) + " bytes is neither the fp32 blob (" +
+                                        std::to_string(a->nparams * 4) + ") nor the bf16 blob (" +
+                                        std::to_string(a->nparams * 2) + ")");
+    }
+    FI_HIP_CHECK(hipMemcpyAsync(a->params, p, a->nparams * 4, hipMemcpyHostToDevice, a->stream));
+    if (a->atari) FI_TRY(atari_sync_weights(a->atari, a->params, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    a->version = version;
+    a->have_params = true;
+    return FI_OK;
+}
+
+extern "C" int fi_actor_set_params(fi_actor* a, const void* blob, size_t bytes, uint64_t version) {
+    try {
+        return set_params(a, blob, bytes, version);
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_OOM, std::string("actor_set_params: ") + e.what());
+    }
+}
+
+extern "C" int fi_actor_set_mode(fi_actor* a, int mode) {
+    FI_REQUIRE(a, "actor_set_mode: null actor");
+    FI_REQUIRE(mode == FI_ACT_SAMPLE || mode == FI_ACT_GREEDY, "actor_set_mode: unknown mode");
+    a->mode = mode;
+    return FI_OK;
+}
+
+extern "C" int fi_actor_seed(fi_actor* a, uint64_t seed, uint64_t draw) {
+    FI_REQUIRE(a, "actor_seed: null actor");
+    a->seed = seed;
+    a->draw = draw;
+    return FI_OK;
+}
+
+// ------------------------------------------------------------------ the act call
+static int mlp_forward(fi_actor* a, float* logits, float* values) {
+    const int D = a->D, H = a->H, A = a->A;
+    const float* W1 = a->params;
+    const float* b1 = W1 + (size_t)D * H;
+    const float* W2 = b1 + H;
+    const float* b2 = W2 + (size_t)H * H;
+    const float* Wh = b2 + H;
+    const float* bh = Wh + (size_t)H * (A + 1);
+    FI_TRY(f32_linear_fwd(a->obs, a->N, D, W1, b1, H, true, a->h1, a->stream));
+    FI_TRY(f32_linear_fwd(a->h1, a->N, H, W2, b2, H, true, a->h2, a->stream));
+    FI_TRY(f32_heads_fwd(a->h2, a->N, H, Wh, bh, A, logits, values, a->stream));
+    return FI_OK;
+}
+
+static void mark(fi_actor* a, int i) {
+    if (a->profiling) (void)hipEventRecord(a->ev[i], a->stream);
+}
+
+static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int32_t* actions, float* logits,
+               float* values) {
+    static const char* const names[] = {"actor_act_obs", "actor_act_frames", "actor_act_planes"};
+    const std::string nm = names[kind];
+    FI_REQUIRE(a, nm + ": null actor");
+    if (kind == IN_OBS)
+        FI_REQUIRE(a->cfg.arch == FI_ARCH_MLP, nm + ": an Atari handle takes frames or planes (fi_actor_act_frames, "
+                                                    "fi_actor_act_planes), not an observation vector");
+    else
+        FI_REQUIRE(a->cfg.arch == FI_ARCH_ATARI, nm + ": an MLP handle takes observation vectors (fi_actor_act_obs)");
+    FI_REQUIRE(in && (kind != IN_PLANES || start), nm + ": null input");
+    if (!a->have_params)
+        return fail(FI_ERR_STATE, nm + ": no parameters yet (fi_actor_set_params with the learner's published blob)");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    const size_t N = a->N, A = a->A;
+    void* dst = nullptr;
+    size_t bytes = 0;
+    if (kind == IN_OBS) {
+        dst = a->obs;
+        bytes = N * a->D * sizeof(float);
+        std::memcpy(a->pin_in, in, bytes);
+    } else if (kind == IN_FRAMES) {
+        dst = a->frames;
+        bytes = N * kStackBytes;
+        std::memcpy(a->pin_in, in, bytes);
+    } else {  // the planes, then the flags: one copy
+        dst = a->planes;
+        bytes = N * kPlaneBytes + N;
+        std::memcpy(a->pin_in, in, N * kPlaneBytes);
+        std::memcpy(a->pin_in + N * kPlaneBytes, start, N);
+    }
+    int32_t* d_act = (int32_t*)a->out;
+    float* d_val = (float*)(a->out + a->off_val);
+    float* d_log = (float*)(a->out + a->off_log);
+    int* d_bad = (int*)(a->out + a->off_bad);
+    mark(a, PH_H2D);
+    FI_HIP_CHECK(hipMemcpyAsync(dst, a->pin_in, bytes, hipMemcpyHostToDevice, a->stream));
+    mark(a, PH_PUSH);
+    if (kind == IN_PLANES) FI_TRY(push_planes_launch(a->stacks, a->planes, a->planes + N * kPlaneBytes, a->N, a->stream));
+    mark(a, PH_FWD);
+    if (kind == IN_OBS) FI_TRY(mlp_forward(a, d_log, d_val));
+    else FI_TRY(atari_forward(a->atari, kind == IN_PLANES ? a->stacks : a->frames, d_log, d_val, a->stream));
+    mark(a, PH_SAMPLE);
+    FI_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), a->stream));
+    FI_TRY(sample_actions_launch(d_log, a->N, a->A, a->mode, a->seed, a->draw, d_act, d_bad, a->stream));
+    mark(a, PH_D2H);
+    FI_HIP_CHECK(hipMemcpyAsync(a->pin_out, a->out, a->out_bytes, hipMemcpyDeviceToHost, a->stream));
+    mark(a, PH_COUNT);
+    a->draw++;
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    if (a->profiling) {
+        for (int p = 0; p < PH_COUNT; ++p) {
+            float ms = 0.f;
+            FI_HIP_CHECK(hipEventElapsedTime(&ms, a->ev[p], a->ev[p + 1]));
+            a->phase_sum[p] += ms;
+        }
+        a->phase_calls++;
+    }
+    if (actions) std::memcpy(actions, a->pin_out, N * sizeof(int32_t));
+    if (values) std::memcpy(values, a->pin_out + a->off_val, N * sizeof(float));
+    if (logits) std::memcpy(logits, a->pin_out + a->off_log, N * A * sizeof(float));
+    int bad = 0;
+    std::memcpy(&bad, a->pin_out + a->off_bad, sizeof(int));
+    if (bad != 0)
+        return fail(FI_ERR_NONFINITE, nm + ": " + std::to_string(bad) + " of " + std::to_string(N) +
+                                          " rows hold NaN / Inf logits (their action is 0)");
+    return FI_OK;
+}
+
+extern "C" int fi_actor_act_obs(fi_actor* a, const float* obs, int32_t* actions, float* logits, float* values) {
+    return act(a, IN_OBS, obs, nullptr, actions, logits, values);
+}
+extern "C" int fi_actor_act_frames(fi_actor* a, const uint8_t* frames, int32_t* actions, float* logits,
+                                   float* values) {
+    return act(a, IN_FRAMES, frames, nullptr, actions, logits, values);
+}
+extern "C" int fi_actor_act_planes(fi_actor* a, const uint8_t* planes, const uint8_t* episode_start, int32_t* actions,
+                                   float* logits, float* values) {
+    return act(a, IN_PLANES, planes, episode_start, actions, logits, values);
+}
+
+extern "C" int fi_actor_reset_stacks(fi_actor* a) {
+    FI_REQUIRE(a, "actor_reset_stacks: null actor");
+    FI_REQUIRE(a->stacks, "actor_reset_stacks: only an Atari handle has stacks");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_HIP_CHECK(hipMemsetAsync(a->stacks, 0, (size_t)a->N * kStackBytes, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    return FI_OK;
+}
+
+extern "C" int fi_actor_read_stacks(fi_actor* a, uint8_t* dst, size_t bytes) {
+    FI_REQUIRE(a && dst, "actor_read_stacks: null argument");
+    FI_REQUIRE(a->stacks, "actor_read_stacks: only an Atari handle has stacks");
+    FI_REQUIRE(bytes == (size_t)a->N * kStackBytes,
+               "actor_read_stacks: bytes != num_envs * 28224 = " + std::to_string((size_t)a->N * kStackBytes));
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_HIP_CHECK(hipMemcpyAsync(dst, a->stacks, bytes, hipMemcpyDeviceToHost, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    return FI_OK;
+}
+
+extern "C" int fi_actor_set_profiling(fi_actor* a, int on) {
+    FI_REQUIRE(a, "actor_set_profiling: null actor");
+    a->profiling = on != 0;
+    for (double& s : a->phase_sum) s = 0.0;
+    a->phase_calls = 0;
+    return FI_OK;
+}
+
+extern "C" int fi_actor_phase_times(fi_actor* a, float* ms, int n, int* n_calls) {
+    FI_REQUIRE(a && ms && n >= 1, "actor_phase_times: bad arguments");
+    for (int p = 0; p < n && p < PH_COUNT; ++p)
+        ms[p] = a->phase_calls ? (float)(a->phase_sum[p] / a->phase_calls) : 0.f;
+    if (n_calls) *n_calls = a->phase_calls;
+    for (double& s : a->phase_sum) s = 0.0;
+    a->phase_calls = 0;
+    return FI_OK;
+}
+
+// ------------------------------------------------------------------ standalone kernels
+extern "C" int fi_push_planes(uint8_t* stacks_dev, const uint8_t* planes_dev, const uint8_t* episode_start_dev, int N,
+                              void* stream) {
+    return push_planes_launch(stacks_dev, planes_dev, episode_start_dev, N, (hipStream_t)stream);
+}
+
+extern "C" int fi_sample_actions(const float* logits_dev, int N, int A, int mode, uint64_t seed, uint64_t draw,
+                                 int32_t* actions_dev, int* nonfinite_dev, void* stream) {
+    return sample_actions_launch(logits_dev, N, A, mode, seed, draw, actions_dev, nonfinite_dev, (hipStream_t)stream);
+}

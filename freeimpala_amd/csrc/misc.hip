@@ -12,29 +12,12 @@
 
 namespace fi {
 
-// ---------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ uint4 philox4(uint64_t seed, uint64_t e, uint32_t stream) {
-    uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(e >> 32), c2 = stream, c3 = 0u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
+// philox4 and the stream ids (ST_*): fi_common.h, shared with actor.hip's sampler
 __device__ __forceinline__ float approx_normal(uint4 u) {
     const uint32_t s = (u.x >> 8) + (u.y >> 8) + (u.z >> 8) + (u.w >> 8);
     const float x = (float)((int32_t)s - (int32_t)(1u << 25));
     return x * 0x1.bb67aep-24f;
 }
-
-enum { ST_OBS = 0, ST_MU = 1, ST_ACT = 2, ST_REW = 3, ST_DONE = 4, ST_FRAME = 5 };
 
 __global__ void synth_normal_kernel(uint64_t seed, uint32_t stream, int rows, int B, int B_glob,
                                     int b_off, int D, float* out) {

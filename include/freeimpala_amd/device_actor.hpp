@@ -1,0 +1,124 @@
+// device_actor.hpp -- C++ host side of batched policy inference (include/fi_actor.h).
+//
+// What an actor process needs to turn observations into actions with the policy the learner
+// publishes: a DeviceActor owns one fi_actor handle (N environments per call, one HIP stream),
+// takes the published blob (DeviceLearner::publish / ModelManager's bytes) and returns actions,
+// the policy's logits (the mu field of the records it writes) and values. Failures of an act call
+// never throw: it returns false and last_error() holds the message, as DeviceLearner::step does.
+// Construction throws std::runtime_error when the HIP library or device is unusable -- there is
+// no CPU fallback. One thread at a time per DeviceActor.
+#pragma once
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "fi_actor.h"
+
+namespace freeimpala_amd {
+
+struct ActorConfig {
+    std::string arch = "mlp";  // mlp|atari
+    int num_envs = 1;          // N environments per act call
+    int num_actions = 18;
+    int obs_dim = 128;
+    int hidden = 256;
+    bool greedy = false;       // argmax instead of a draw
+    uint64_t seed = 0;         // key of the action draws
+    int device = 0;
+
+    fi_actor_config abi_config() const {
+        fi_actor_config c;
+        fi_actor_config_init(&c);
+        c.arch = arch == "atari" ? FI_ARCH_ATARI : FI_ARCH_MLP;
+        c.num_envs = num_envs;
+        c.num_actions = num_actions;
+        c.obs_dim = obs_dim;
+        c.hidden = hidden;
+        c.mode = greedy ? FI_ACT_GREEDY : FI_ACT_SAMPLE;
+        c.seed = seed;
+        c.device = device;
+        return c;
+    }
+};
+
+struct ActResult {
+    std::vector<int32_t> actions;  // N
+    std::vector<float> logits;     // N * A
+    std::vector<float> values;     // N
+};
+
+class DeviceActor {
+public:
+    static constexpr size_t kPlaneBytes = 84 * 84, kFrameBytes = 4 * kPlaneBytes;
+
+    explicit DeviceActor(const ActorConfig& cfg) : cfg_(cfg) {
+        if (cfg.arch != "mlp" && cfg.arch != "atari") throw std::invalid_argument("ActorConfig.arch: mlp|atari");
+        const fi_actor_config c = cfg.abi_config();
+        if (fi_actor_create(&c, &h_) != FI_OK) throw std::runtime_error(std::string("fi_actor_create: ") + fi_last_error());
+    }
+    ~DeviceActor() { fi_actor_destroy(h_); }
+    DeviceActor(const DeviceActor&) = delete;
+    DeviceActor& operator=(const DeviceActor&) = delete;
+
+    const ActorConfig& config() const { return cfg_; }
+    size_t param_count() const { return fi_actor_param_count(h_); }
+    uint64_t version() const { return fi_actor_version(h_); }
+    const std::string& last_error() const { return err_; }
+
+    // the blob DeviceLearner::publish fills (fp32 or bf16) and its version
+    bool load(const std::vector<char>& blob, uint64_t version) {
+        return ok(fi_actor_set_params(h_, blob.data(), blob.size(), version));
+    }
+    bool set_greedy(bool greedy) { return ok(fi_actor_set_mode(h_, greedy ? FI_ACT_GREEDY : FI_ACT_SAMPLE)); }
+    bool seed(uint64_t seed, uint64_t draw = 0) { return ok(fi_actor_seed(h_, seed, draw)); }
+
+    // obs: N * obs_dim floats (MLP)
+    bool act_obs(const std::vector<float>& obs, ActResult& out) {
+        if (obs.size() != (size_t)cfg_.num_envs * cfg_.obs_dim) return bad("act_obs: obs must hold num_envs * obs_dim floats");
+        size(out);
+        return ok(fi_actor_act_obs(h_, obs.data(), out.actions.data(), out.logits.data(), out.values.data()));
+    }
+    // frames: N stacks of 84x84x4 bytes (Atari)
+    bool act_frames(const std::vector<uint8_t>& frames, ActResult& out) {
+        if (frames.size() != (size_t)cfg_.num_envs * kFrameBytes) return bad("act_frames: frames must hold num_envs * 28224 bytes");
+        size(out);
+        return ok(fi_actor_act_frames(h_, frames.data(), out.actions.data(), out.logits.data(), out.values.data()));
+    }
+    // planes: N newest 84x84 observations; episode_start: N flags (Atari; the stacks stay on the device)
+    bool act_planes(const std::vector<uint8_t>& planes, const std::vector<uint8_t>& episode_start, ActResult& out) {
+        if (planes.size() != (size_t)cfg_.num_envs * kPlaneBytes || episode_start.size() != (size_t)cfg_.num_envs)
+            return bad("act_planes: planes must hold num_envs * 7056 bytes and episode_start num_envs flags");
+        size(out);
+        return ok(fi_actor_act_planes(h_, planes.data(), episode_start.data(), out.actions.data(), out.logits.data(),
+                                      out.values.data()));
+    }
+    bool reset_stacks() { return ok(fi_actor_reset_stacks(h_)); }
+    bool read_stacks(std::vector<uint8_t>& out) {
+        out.resize((size_t)cfg_.num_envs * kFrameBytes);
+        return ok(fi_actor_read_stacks(h_, out.data(), out.size()));
+    }
+
+private:
+    void size(ActResult& out) const {
+        out.actions.resize((size_t)cfg_.num_envs);
+        out.logits.resize((size_t)cfg_.num_envs * cfg_.num_actions);
+        out.values.resize((size_t)cfg_.num_envs);
+    }
+    bool ok(int rc) {
+        if (rc == FI_OK) return true;
+        err_ = fi_last_error();
+        return false;
+    }
+    bool bad(const char* msg) {
+        err_ = msg;
+        return false;
+    }
+
+    ActorConfig cfg_;
+    fi_actor* h_ = nullptr;
+    std::string err_;
+};
+
+}  // namespace freeimpala_amd
