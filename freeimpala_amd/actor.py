@@ -171,6 +171,52 @@ class Actor:
         check(lib().fi_actor_read_stacks(self._h, out.ctypes.data, out.nbytes), "fi_actor_read_stacks")
         return out
 
+    # --- rollout recording (include/fi_rollout.h; the rule: freeimpala_amd/rollout.py)
+    def begin_rollout(self, T: int) -> None:
+        """From here on every act_planes / act_obs call records its step on the device, T steps to
+        an unroll; two buffers of N entries are allocated."""
+        from . import rollout
+        check(rollout.lib().fi_rollout_begin(self._h, T), "fi_rollout_begin")
+
+    def outcome(self, rewards, discounts) -> None:
+        """The rewards and discounts (N each) the environments returned for the last act call's actions."""
+        from . import rollout
+        rew = self._input(rewards, np.float32, (self.N,), "rewards")
+        disc = self._input(discounts, np.float32, (self.N,), "discounts")
+        check(rollout.lib().fi_rollout_outcome(self._h, rew.ctypes.data, disc.ctypes.data), "fi_rollout_outcome")
+
+    def rollout_ready(self) -> bool:
+        from . import rollout
+        return bool(rollout.lib().fi_rollout_ready(self._h))
+
+    @property
+    def rollout_entry_bytes(self) -> int:
+        from . import rollout
+        return int(rollout.lib().fi_rollout_entry_bytes(self._h))
+
+    def acquire_rollout(self) -> tuple[int, int, int]:
+        """(device pointer, entry stride, ready event) of the completed unroll."""
+        from . import rollout
+        ptr, stride, ev = _P(), C.c_size_t(), _P()
+        check(rollout.lib().fi_rollout_acquire(self._h, C.byref(ptr), C.byref(stride), C.byref(ev)),
+              "fi_rollout_acquire")
+        return ptr.value, stride.value, ev.value
+
+    def release_rollout(self, consumed_event=None) -> None:
+        from . import rollout
+        check(rollout.lib().fi_rollout_release(self._h, consumed_event), "fi_rollout_release")
+
+    def read_rollout(self) -> np.ndarray:
+        """The completed unroll's entries, (N, entry_bytes) uint8; it stays unreleased."""
+        from . import rollout
+        out = np.empty((self.N, self.rollout_entry_bytes), np.uint8)
+        check(rollout.lib().fi_rollout_read(self._h, out.ctypes.data, out.nbytes), "fi_rollout_read")
+        return out
+
+    def end_rollout(self) -> None:
+        from . import rollout
+        check(rollout.lib().fi_rollout_end(self._h), "fi_rollout_end")
+
     # --- profiling
     def set_profiling(self, on: bool) -> None:
         check(lib().fi_actor_set_profiling(self._h, int(on)), "fi_actor_set_profiling")

@@ -8,6 +8,8 @@
 //     f32_heads_fwd on N rows), unchanged, so a row's logits are the bits the learner computes
 //   * sample_actions_kernel: one categorical draw (or the argmax) per row, a counter-based rule a
 //     host reference reproduces (fi_actor.h)
+//   * a recording handle (fi_rollout.h) also writes every step into the learner's entry format in
+//     device memory, with the kernels of rollout.hip, and hands completed unrolls to a learner
 // One HIP stream per handle, no global mutable state, no HIP graphs.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +23,7 @@
 #include "atari.h"
 #include "fi_actor.h"
 #include "fi_common.h"
+#include "fi_rollout.h"
 #include "kernels.h"
 
 namespace fi {
@@ -226,6 +229,21 @@ struct fi_actor {
     double phase_sum[PH_COUNT] = {};
     int phase_calls = 0;
     std::vector<void*> allocs;
+    // rollout recording (fi_rollout.h): two device buffers of N entries; buf[fill] takes the unroll
+    // being acted, buf[ready] (or -1) holds a completed unroll until it is released
+    struct {
+        int T = 0;  // 0: not recording
+        size_t rec = 0, entry = 0;
+        char* buf[2] = {nullptr, nullptr};
+        hipEvent_t ready_ev[2] = {nullptr, nullptr};
+        int fill = 0;
+        int t = 0;              // the record of buf[fill] the next act call writes, 0..T
+        int ready = -1;
+        bool need_outcome = false;  // a step was recorded and its outcome not yet supplied
+        int last_buf = -1, last_t = 0;  // where the last act call's whole step went
+        float* outcome = nullptr;       // device: N rewards, N discounts
+        float* pin_outcome = nullptr;
+    } ro;
 };
 
 static int dalloc(fi_actor* a, void** p, size_t bytes) {
@@ -238,9 +256,20 @@ static int dalloc(fi_actor* a, void** p, size_t bytes) {
     return FI_OK;
 }
 
+static void rollout_free(fi_actor* a) {
+    for (int i = 0; i < 2; ++i) {
+        if (a->ro.buf[i]) (void)hipFree(a->ro.buf[i]);
+        if (a->ro.ready_ev[i]) (void)hipEventDestroy(a->ro.ready_ev[i]);
+    }
+    if (a->ro.outcome) (void)hipFree(a->ro.outcome);
+    if (a->ro.pin_outcome) (void)hipHostFree(a->ro.pin_outcome);
+    a->ro = {};
+}
+
 static void destroy(fi_actor* a) {
     if (!a) return;
     if (a->stream) (void)hipStreamSynchronize(a->stream);
+    rollout_free(a);
     atari_destroy(a->atari);
     for (void* p : a->allocs) (void)hipFree(p);
     if (a->pin_in) (void)hipHostFree(a->pin_in);
@@ -426,6 +455,41 @@ static int mlp_forward(fi_actor* a, float* logits, float* values) {
     return FI_OK;
 }
 
+// One act call's records (fi_rollout.h, the recording rule), enqueued on the handle's stream. The
+// call's device tensors -- planes and flags (obs), logits, actions, the stacks -- stay as they are
+// until the next act call's H2D copy, which follows in stream order.
+static int record_step(fi_actor* a, int kind, bool completing, const float* d_log, const int32_t* d_act) {
+    auto& ro = a->ro;
+    const uint32_t flags = (uint32_t)a->version;
+    const uint8_t* d_start = a->planes ? a->planes + (size_t)a->N * kPlaneBytes : nullptr;
+    auto put = [&](int b, int t, bool whole) -> int {
+        if (kind == IN_PLANES)
+            return record_planes_launch(ro.buf[b], ro.entry, t, a->planes, d_start, whole ? d_log : nullptr,
+                                        whole ? d_act : nullptr, flags, a->N, a->A, a->stream);
+        return record_obs_launch(ro.buf[b], ro.entry, t, a->obs, a->D, whole ? d_log : nullptr,
+                                 whole ? d_act : nullptr, flags, a->N, a->A, a->stream);
+    };
+    int b = ro.fill, t = ro.t;
+    if (completing) {
+        FI_TRY(put(ro.fill, ro.T, false));  // record T: the bootstrap plane and episode_start only
+        b = ro.fill ^ 1;
+        t = 0;
+    }
+    FI_TRY(put(b, t, true));
+    if (t == 0 && kind == IN_PLANES)
+        FI_TRY(extract_history_launch(ro.buf[b], ro.entry, (size_t)(ro.T + 1) * ro.rec, a->stacks, a->N, a->stream));
+    if (completing) {
+        FI_HIP_CHECK(hipEventRecord(ro.ready_ev[ro.fill], a->stream));
+        ro.ready = ro.fill;
+        ro.fill = b;
+    }
+    ro.last_buf = b;
+    ro.last_t = t;
+    ro.t = t + 1;
+    ro.need_outcome = true;
+    return FI_OK;
+}
+
 static void mark(fi_actor* a, int i) {
     if (a->profiling) (void)hipEventRecord(a->ev[i], a->stream);
 }
@@ -443,6 +507,19 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     FI_REQUIRE(in && (kind != IN_PLANES || start), nm + ": null input");
     if (!a->have_params)
         return fail(FI_ERR_STATE, nm + ": no parameters yet (fi_actor_set_params with the learner's published blob)");
+    // a recording handle refuses before anything is enqueued or pushed
+    const bool recording = a->ro.T > 0;
+    const bool completing = recording && a->ro.t == a->ro.T;  // the (T+1)-th call of the unroll being filled
+    if (recording) {
+        FI_REQUIRE(kind != IN_FRAMES, nm + ": the handle records a rollout, and stacked records are not produced "
+                                           "(fi_actor_act_planes, or fi_rollout_end first)");
+        if (a->ro.need_outcome)
+            return fail(FI_ERR_STATE, nm + ": the previous step's rewards and discounts were never supplied "
+                                           "(fi_rollout_outcome after every act call of a recording handle)");
+        if (completing && a->ro.ready >= 0)
+            return fail(FI_ERR_STATE, nm + ": this call completes an unroll, and the previous one has not been "
+                                           "released: its buffer takes the next unroll's record 0 (fi_rollout_release)");
+    }
     FI_HIP_CHECK(hipSetDevice(a->dev));
     const size_t N = a->N, A = a->A;
     void* dst = nullptr;
@@ -480,6 +557,9 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     mark(a, PH_COUNT);
     a->draw++;
     FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    // after the outputs' copy and the wait for it: the record kernels sit in none of the profiled
+    // phases and the caller does not wait for them
+    if (recording) FI_TRY(record_step(a, kind, completing, d_log, d_act));
     if (a->profiling) {
         for (int p = 0; p < PH_COUNT; ++p) {
             float ms = 0.f;
@@ -514,6 +594,10 @@ extern "C" int fi_actor_act_planes(fi_actor* a, const uint8_t* planes, const uin
 extern "C" int fi_actor_reset_stacks(fi_actor* a) {
     FI_REQUIRE(a, "actor_reset_stacks: null actor");
     FI_REQUIRE(a->stacks, "actor_reset_stacks: only an Atari handle has stacks");
+    if (a->ro.T > 0)
+        return fail(FI_ERR_STATE, "actor_reset_stacks: the handle records a rollout, and a reset would break the "
+                                  "history the learner rebuilds (start an episode with episode_start, or "
+                                  "fi_rollout_end first)");
     FI_HIP_CHECK(hipSetDevice(a->dev));
     FI_HIP_CHECK(hipMemsetAsync(a->stacks, 0, (size_t)a->N * kStackBytes, a->stream));
     FI_HIP_CHECK(hipStreamSynchronize(a->stream));
@@ -558,4 +642,158 @@ extern "C" int fi_push_planes(uint8_t* stacks_dev, const uint8_t* planes_dev, co
 extern "C" int fi_sample_actions(const float* logits_dev, int N, int A, int mode, uint64_t seed, uint64_t draw,
                                  int32_t* actions_dev, int* nonfinite_dev, void* stream) {
     return sample_actions_launch(logits_dev, N, A, mode, seed, draw, actions_dev, nonfinite_dev, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ rollout recording (fi_rollout.h)
+
+static int rollout_begin(fi_actor* a, int32_t T) {
+    FI_REQUIRE(a, "rollout_begin: null actor");
+    FI_REQUIRE(T >= 1 && T <= (1 << 20), "rollout_begin: seq_len must be >= 1");
+    if (a->ro.T > 0) return fail(FI_ERR_STATE, "rollout_begin: the handle records already (fi_rollout_end first)");
+    const bool atari = a->cfg.arch == FI_ARCH_ATARI;
+    FI_REQUIRE(!atari || a->A <= 18, "rollout_begin: the plane record's header holds mu[18]");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    auto& ro = a->ro;
+    ro.rec = atari ? (size_t)FI_ATARI_PLANE_RECORD_BYTES : (size_t)FI_RECORD_BYTES;
+    ro.entry = (size_t)(T + 1) * ro.rec + (atari ? (size_t)FI_ATARI_HISTORY_BYTES : 0);
+    const size_t bytes = (size_t)a->N * ro.entry;
+    struct Guard {
+        fi_actor* a;
+        bool ok = false;
+        ~Guard() { if (!ok) rollout_free(a); }
+    } guard{a};
+    for (int i = 0; i < 2; ++i) {
+        const hipError_t e = hipMalloc((void**)&ro.buf[i], bytes);
+        if (e != hipSuccess) {
+            ro.buf[i] = nullptr;
+            (void)hipGetLastError();
+            return fail(FI_ERR_OOM, "rollout_begin: hipMalloc(" + std::to_string(bytes) + ") for rollout buffer " +
+                                        std::to_string(i) + " of 2: " + hipGetErrorString(e));
+        }
+        FI_HIP_CHECK(hipMemsetAsync(ro.buf[i], 0, bytes, a->stream));
+        FI_HIP_CHECK(hipEventCreateWithFlags(&ro.ready_ev[i], hipEventDisableTiming));
+    }
+    const size_t ob = 2 * (size_t)a->N * sizeof(float);
+    if (hipMalloc((void**)&ro.outcome, ob) != hipSuccess || hipHostMalloc((void**)&ro.pin_outcome, ob, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FI_ERR_OOM, "rollout_begin: the outcome staging (" + std::to_string(ob) + " bytes) cannot be allocated");
+    }
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    ro.T = T;
+    ro.fill = 0;
+    ro.t = 0;
+    ro.ready = -1;
+    ro.need_outcome = false;
+    ro.last_buf = -1;
+    guard.ok = true;
+    return FI_OK;
+}
+
+extern "C" int fi_rollout_begin(fi_actor* a, int32_t seq_len) {
+    try {
+        return rollout_begin(a, seq_len);
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_OOM, std::string("rollout_begin: ") + e.what());
+    }
+}
+
+extern "C" int fi_rollout_outcome(fi_actor* a, const float* rewards, const float* discounts) {
+    FI_REQUIRE(a && rewards && discounts, "rollout_outcome: null argument");
+    auto& ro = a->ro;
+    if (ro.T == 0) return fail(FI_ERR_STATE, "rollout_outcome: the handle does not record (fi_rollout_begin)");
+    if (!ro.need_outcome)
+        return fail(FI_ERR_STATE, "rollout_outcome: no act call since the last outcome: every step takes one");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    // the pinned block is free: the act call between two outcomes has waited for the stream
+    const size_t N = a->N;
+    std::memcpy(ro.pin_outcome, rewards, N * sizeof(float));
+    std::memcpy(ro.pin_outcome + N, discounts, N * sizeof(float));
+    FI_HIP_CHECK(hipMemcpyAsync(ro.outcome, ro.pin_outcome, 2 * N * sizeof(float), hipMemcpyHostToDevice, a->stream));
+    const bool atari = a->cfg.arch == FI_ARCH_ATARI;
+    const size_t field = (size_t)ro.last_t * ro.rec + (atari ? kPlaneRecReward : kMlpRecReward);
+    FI_TRY(scatter_outcome_launch(ro.buf[ro.last_buf], ro.entry, field, ro.outcome, a->N, a->stream));
+    ro.need_outcome = false;
+    return FI_OK;
+}
+
+extern "C" int fi_rollout_ready(const fi_actor* a) { return a && a->ro.T > 0 && a->ro.ready >= 0 ? 1 : 0; }
+extern "C" size_t fi_rollout_entry_bytes(const fi_actor* a) { return a && a->ro.T > 0 ? a->ro.entry : 0; }
+
+static int no_unroll(const fi_actor* a, const char* who) {
+    if (a->ro.T == 0) return fail(FI_ERR_STATE, std::string(who) + ": the handle does not record (fi_rollout_begin)");
+    return fail(FI_ERR_STATE, std::string(who) + ": no completed unroll waits (record " + std::to_string(a->ro.t) +
+                                  " of " + std::to_string(a->ro.T + 1) + " is next)");
+}
+
+extern "C" int fi_rollout_acquire(fi_actor* a, const void** entries_dev, size_t* entry_stride, void** ready_event) {
+    FI_REQUIRE(a, "rollout_acquire: null actor");
+    if (a->ro.T == 0 || a->ro.ready < 0) return no_unroll(a, "rollout_acquire");
+    if (entries_dev) *entries_dev = a->ro.buf[a->ro.ready];
+    if (entry_stride) *entry_stride = a->ro.entry;
+    if (ready_event) *ready_event = (void*)a->ro.ready_ev[a->ro.ready];
+    return FI_OK;
+}
+
+extern "C" int fi_rollout_release(fi_actor* a, void* consumed_event) {
+    FI_REQUIRE(a, "rollout_release: null actor");
+    if (a->ro.T == 0 || a->ro.ready < 0) return no_unroll(a, "rollout_release");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    // everything the stream does from here on, the next write to that buffer included, follows the event
+    if (consumed_event) FI_HIP_CHECK(hipStreamWaitEvent(a->stream, (hipEvent_t)consumed_event, 0));
+    a->ro.ready = -1;
+    return FI_OK;
+}
+
+extern "C" int fi_rollout_read(fi_actor* a, void* host_dst, size_t bytes) {
+    FI_REQUIRE(a && host_dst, "rollout_read: null argument");
+    if (a->ro.T == 0 || a->ro.ready < 0) return no_unroll(a, "rollout_read");
+    const size_t want = (size_t)a->N * a->ro.entry;
+    FI_REQUIRE(bytes == want, "rollout_read: bytes != num_envs * entry bytes = " + std::to_string(want));
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_HIP_CHECK(hipMemcpyAsync(host_dst, a->ro.buf[a->ro.ready], bytes, hipMemcpyDeviceToHost, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    return FI_OK;
+}
+
+extern "C" int fi_rollout_end(fi_actor* a) {
+    FI_REQUIRE(a, "rollout_end: null actor");
+    if (a->ro.T == 0) return FI_OK;
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    rollout_free(a);
+    return FI_OK;
+}
+
+// acquire, step, release. It lives here, not in learner.cpp, because it holds both handles: the
+// learner is driven through its C ABI, and learner.cpp stays free of the actor.
+extern "C" int fi_learner_step_rollout(fi_learner* l, fi_actor* a, fi_step_stats* out) {
+    FI_REQUIRE(l && a, "step_rollout: null argument");
+    LearnerInfo li{};
+    FI_TRY(learner_info(l, &li));
+    if (a->ro.T == 0) return fail(FI_ERR_STATE, "step_rollout: the actor does not record (fi_rollout_begin)");
+    auto differs = [&](const char* what, int actor, int learner) {
+        return fail(FI_ERR_INVALID, std::string("step_rollout: the actor's ") + what + " " + std::to_string(actor) +
+                                        " != the learner's " + std::to_string(learner));
+    };
+    if (a->dev != li.dev) return differs("device", a->dev, li.dev);
+    if (a->cfg.arch != li.arch) return differs("arch", a->cfg.arch, li.arch);
+    if (a->A != li.A) return differs("num_actions", a->A, li.A);
+    if (li.arch == FI_ARCH_MLP && a->D != li.D) return differs("obs_dim", a->D, li.D);
+    if (a->N != li.B) return differs("num_envs", a->N, li.B);  // the learner's batch
+    if (a->ro.T != li.T) return differs("rollout seq_len", a->ro.T, li.T);
+    FI_REQUIRE(li.dev_entries_ok, "step_rollout: an Atari handle reads device entries in the planes format only "
+                                  "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    const void* entries = nullptr;
+    size_t stride = 0;
+    void* ready = nullptr;
+    FI_TRY(fi_rollout_acquire(a, &entries, &stride, &ready));
+    const int rc = fi_learner_step_entries_dev(l, entries, stride, ready, out);
+    // FI_ERR_INVALID / FI_ERR_STATE / FI_ERR_HIP / FI_ERR_OOM: refused or broken before or at the enqueue,
+    // the unroll stays. Otherwise the step ran (and was waited for), whatever it then reported
+    // (FI_ERR_NONFINITE: update skipped): the ingest has read the buffer, and it goes back.
+    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
+    std::string why;
+    if (rc != FI_OK) why = fi_last_error();
+    FI_TRY(fi_rollout_release(a, fi_learner_entries_consumed_event(l)));
+    return rc == FI_OK ? FI_OK : fail(rc, why);
 }

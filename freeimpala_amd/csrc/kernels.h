@@ -94,4 +94,24 @@ int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entr
                                float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
                                int* bad = nullptr);
 
+// rollout.hip: one acting step into the learner's entry format (include/fi_rollout.h). logits ==
+// nullptr: the plane and episode_start (the observation) only
+int record_planes_launch(void* entries, size_t stride, int t, const uint8_t* planes, const uint8_t* start,
+                         const float* logits, const int32_t* actions, uint32_t flags, int N, int A, hipStream_t s);
+int extract_history_launch(void* entries, size_t stride, size_t hist_off, const uint8_t* stacks, int N, hipStream_t s);
+int record_obs_launch(void* entries, size_t stride, int t, const float* obs, int D, const float* logits,
+                      const int32_t* actions, uint32_t flags, int N, int A, hipStream_t s);
+// out: N rewards then N discounts; field: byte offset of the reward in entry 0 (the record's
+// offset plus the reward's in a record: the discount follows it)
+constexpr size_t kPlaneRecReward = 7132, kMlpRecReward = 772;
+int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* out, int N, hipStream_t s);
+
+// learner.cpp: what fi_learner_step_rollout (actor.hip: it holds both handles) compares with the
+// actor. learner.cpp itself calls nothing of actor.hip, so a library of the learner alone links
+struct LearnerInfo {
+    int dev, arch, B, A, D, T;
+    bool dev_entries_ok;  // MLP, or Atari in the planes format
+};
+int learner_info(const fi_learner* l, LearnerInfo* out);
+
 }  // namespace fi

@@ -24,6 +24,7 @@
 
 #include "atari.h"
 #include "fi_common.h"
+#include "fi_rollout.h"
 #include "kernels.h"
 
 namespace fi {
@@ -94,6 +95,8 @@ struct fi_learner {
     size_t rec_bytes = 0;
     size_t rec_entry_bytes = 0;
     int rec_format = FI_RECORDS_STACKED;  // Atari host entries: whole stacks, or single planes
+    // entries already in device memory (fi_rollout.h): recorded after the ingest that read them
+    hipEvent_t entries_consumed = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -200,6 +203,7 @@ static void destroy(fi_learner* l) {
     if (l->copy_stream) hipStreamSynchronize(l->copy_stream);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
+    if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
     if (l->comm_done) hipEventDestroy(l->comm_done);
     if (l->bad_ready) hipEventDestroy(l->bad_ready);
     if (l->comm_stream) hipStreamDestroy(l->comm_stream);
@@ -282,7 +286,9 @@ static int create(const fi_learner_config* cfg, fi_learner** out) {
         // latency-bound (wgrad_l1 0.44 -> 0.29 ms, wgrad_l2 0.60 -> 0.54 ms; 512 slices measured
         // slower: the slab sums grow)
         l->splits = (int)std::min<size_t>(384, std::max<size_t>(1, rows / 1024));
-        const size_t big = std::max<size_t>((size_t)D * H, (size_t)H * H);
+        // the largest weight gradient: the heads' H x (A + 1) too -- with A + 1 > max(D, H) its slabs
+        // would otherwise run into the bias column sums behind them
+        const size_t big = std::max<size_t>({(size_t)D * H, (size_t)H * H, (size_t)H * (A + 1)});
         l->slab_floats = (size_t)l->splits * (big + 4096);  // wgrad slabs | bias colsum slabs
         FI_TRY(dalloc_n(l, &l->slab, l->slab_floats));
     } else {
@@ -588,13 +594,32 @@ static void fill_stats(fi_learner* l, fi_step_stats* out) {
     out->step_ms = 0.f;
 }
 
-static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out) {
+// entries in device memory, read in place by the ingest (fi_learner_step_entries_dev)
+struct DevEntries {
+    const void* ptr;
+    size_t stride;
+    hipEvent_t ready;
+};
+
+static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, const DevEntries* de = nullptr) {
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_a, l->stream));
     mark(l, FI_PHASE_INGEST);
     FI_HIP_CHECK(hipMemsetAsync(l->bad, 0, sizeof(int), l->stream));
-    if (have_host_batch) {
+    if (de) {
+        if (de->ready) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, de->ready, 0));
+        {
+            Tag t(l, "ingest");
+            if (l->cfg.arch == FI_ARCH_MLP)
+                FI_TRY(ingest_launch(de->ptr, l->T, l->B, l->A, l->D, de->stride, l->obs, l->mu, l->act, l->rew,
+                                     l->disc, l->stream, l->bad));
+            else
+                FI_TRY(ingest_atari_planes_launch(de->ptr, l->T, l->B, l->A, de->stride, l->frames, l->mu, l->act,
+                                                  l->rew, l->disc, l->stream, l->bad));
+        }
+        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
+    } else if (have_host_batch) {
         const int s = l->cur;
         FI_HIP_CHECK(hipStreamWaitEvent(l->stream, l->h2d_done[s], 0));
         {
@@ -899,6 +924,82 @@ extern "C" int fi_learner_wait(fi_learner* l, fi_step_stats* out) {
     l->in_flight = false;
     if (was_in_flight) FI_TRY(check_rejected(l));
     if (out) fill_stats(l, out);  // step_ms = 0: not timed on the asynchronous path
+    return FI_OK;
+}
+
+// ------------------------------------------------------------------ entries in device memory (fi_rollout.h)
+static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, const char* who) {
+    const std::string nm = who;
+    FI_REQUIRE(l && entries, nm + ": null argument");
+    FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
+               nm + ": an Atari handle reads device entries in the planes format only "
+                    "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    const size_t need = entry_bytes_min(l);
+    FI_REQUIRE(stride >= need, nm + ": entry_stride " + std::to_string(stride) + " < " + std::to_string(need) +
+                                   " = fi_learner_entry_bytes()");
+    FI_REQUIRE(stride % 16 == 0 && (uintptr_t)entries % 16 == 0,
+               nm + ": entries_dev and entry_stride must be 16-byte aligned");
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, entries) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != l->dev) {
+        (void)hipGetLastError();
+        return fail(FI_ERR_INVALID, nm + ": entries_dev is not device memory of the handle's device " +
+                                        std::to_string(l->dev));
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)entries) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FI_ERR_INVALID, nm + ": entries_dev lies in no device allocation");
+    }
+    const size_t span = (size_t)(l->B - 1) * stride + need;
+    const size_t have = size - (size_t)((const char*)entries - (const char*)base);
+    FI_REQUIRE(span <= have, nm + ": the allocation ends " + std::to_string(have) + " bytes behind entries_dev, " +
+                                 std::to_string(l->B) + " entries need " + std::to_string(span));
+    if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
+    return FI_OK;
+}
+
+static int step_entries_dev(fi_learner* l, const void* entries, size_t stride, void* ready, fi_step_stats* out,
+                            bool wait, const char* who) {
+    try {
+        FI_TRY(check_dev_entries(l, entries, stride, who));
+        const DevEntries de{entries, stride, (hipEvent_t)ready};
+        if (!wait) {
+            FI_TRY(run_step(l, false, nullptr, &de));
+            l->in_flight = true;
+            return FI_OK;
+        }
+        l->in_flight = false;
+        FI_TRY(run_step(l, false, out, &de));
+        if (!out) {
+            FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+            FI_TRY(check_rejected(l));
+        }
+        return FI_OK;
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
+    }
+}
+
+extern "C" int fi_learner_step_entries_dev(fi_learner* l, const void* entries_dev, size_t entry_stride,
+                                           void* ready_event, fi_step_stats* out) {
+    return step_entries_dev(l, entries_dev, entry_stride, ready_event, out, true, "step_entries_dev");
+}
+
+extern "C" int fi_learner_step_entries_dev_async(fi_learner* l, const void* entries_dev, size_t entry_stride,
+                                                 void* ready_event) {
+    return step_entries_dev(l, entries_dev, entry_stride, ready_event, nullptr, false, "step_entries_dev_async");
+}
+
+extern "C" void* fi_learner_entries_consumed_event(fi_learner* l) { return l ? (void*)l->entries_consumed : nullptr; }
+extern "C" size_t fi_learner_staging_bytes(const fi_learner* l) { return l ? 4 * l->rec_bytes : 0; }
+
+// what fi_learner_step_rollout (actor.hip: it needs both handles) compares with the actor
+int fi::learner_info(const fi_learner* l, LearnerInfo* out) {
+    FI_REQUIRE(l && out, "learner_info: null argument");
+    *out = LearnerInfo{l->dev, l->cfg.arch, l->B, l->A, l->D, l->T,
+                       l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES};
     return FI_OK;
 }
 

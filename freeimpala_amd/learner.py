@@ -140,6 +140,34 @@ class DeviceLearner:
               "fi_learner_step_resident")
         return st.as_dict() if stats else None
 
+    # --- entries already in device memory (include/fi_rollout.h)
+    def step_rollout(self, actor, stats: bool = True) -> dict:
+        """Acquire the actor's completed unroll, step from it in place, release it."""
+        from . import rollout
+        st = _abi.StepStats()
+        check(rollout.lib().fi_learner_step_rollout(self._h, actor._h, C.byref(st) if stats else None),
+              "fi_learner_step_rollout")
+        return st.as_dict() if stats else {}
+
+    def step_entries_dev(self, ptr: int, stride: int, event=None, stats: bool = True) -> dict:
+        """Step from B entries in device memory, `stride` bytes apart, once `event` has completed."""
+        from . import rollout
+        st = _abi.StepStats()
+        check(rollout.lib().fi_learner_step_entries_dev(self._h, ptr, stride, event, C.byref(st) if stats else None),
+              "fi_learner_step_entries_dev")
+        return st.as_dict() if stats else {}
+
+    @property
+    def entries_consumed_event(self) -> int | None:
+        from . import rollout
+        return rollout.lib().fi_learner_entries_consumed_event(self._h)
+
+    @property
+    def staging_bytes(self) -> int:
+        """Pinned plus device bytes of the host-entry staging buffers (0 until a host batch came)."""
+        from . import rollout
+        return int(rollout.lib().fi_learner_staging_bytes(self._h))
+
     def synth(self, seed: int = 42, b_global: int = 0, b_offset: int = 0) -> None:
         check(lib().fi_learner_synth_batch(self._h, seed, b_global, b_offset), "synth")
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fi_actor.h"
+#include "fi_rollout.h"
 
 namespace freeimpala_amd {
 
@@ -99,6 +100,27 @@ public:
         out.resize((size_t)cfg_.num_envs * kFrameBytes);
         return ok(fi_actor_read_stacks(h_, out.data(), out.size()));
     }
+
+    // Rollouts recorded on the device (include/fi_rollout.h): after begin_rollout(T) every act_planes
+    // / act_obs call records its step, outcome() adds the environments' rewards and discounts, and a
+    // learner handle on the same device steps from the completed unroll: fi_learner_step_rollout(
+    // learner, actor.handle(), &stats).
+    bool begin_rollout(int seq_len) { return ok(fi_rollout_begin(h_, seq_len)); }
+    bool outcome(const std::vector<float>& rewards, const std::vector<float>& discounts) {
+        if (rewards.size() != (size_t)cfg_.num_envs || discounts.size() != (size_t)cfg_.num_envs)
+            return bad("outcome: rewards and discounts must hold num_envs floats each");
+        return ok(fi_rollout_outcome(h_, rewards.data(), discounts.data()));
+    }
+    bool rollout_ready() const { return fi_rollout_ready(h_) != 0; }
+    size_t rollout_entry_bytes() const { return fi_rollout_entry_bytes(h_); }
+    // the completed unroll's num_envs entries, back to back; it stays unreleased
+    bool read_rollout(std::vector<uint8_t>& out) {
+        out.resize((size_t)cfg_.num_envs * fi_rollout_entry_bytes(h_));
+        return ok(fi_rollout_read(h_, out.data(), out.size()));
+    }
+    bool release_rollout(void* consumed_event = nullptr) { return ok(fi_rollout_release(h_, consumed_event)); }
+    bool end_rollout() { return ok(fi_rollout_end(h_)); }
+    fi_actor* handle() { return h_; }
 
 private:
     void size(ActResult& out) const {
