@@ -797,3 +797,65 @@ extern "C" int fi_learner_step_rollout(fi_learner* l, fi_actor* a, fi_step_stats
     FI_TRY(fi_rollout_release(a, fi_learner_entries_consumed_event(l)));
     return rc == FI_OK ? FI_OK : fail(rc, why);
 }
+
+// ------------------------------------------------------------------ several actors, one batch (fi_gather.h)
+// Every actor is checked and found ready before the first is acquired, so a refusal leaves every
+// unroll waiting; the learner side (segments, column table, gathering ingest) is learner.cpp's.
+static int step_rollouts(fi_learner* l, fi_actor* const* actors, int32_t n, fi_step_stats* out, bool wait,
+                         const char* who) {
+    const std::string nm = who;
+    FI_REQUIRE(l && actors, nm + ": null argument");
+    FI_REQUIRE(n >= 1 && n <= FI_MAX_SEGMENTS,
+               nm + ": " + std::to_string(n) + " actors, 1 .. " + std::to_string(FI_MAX_SEGMENTS) + " are taken");
+    LearnerInfo li{};
+    FI_TRY(learner_info(l, &li));
+    int64_t envs = 0;
+    for (int k = 0; k < n; ++k) {
+        const fi_actor* a = actors[k];
+        const std::string ak = nm + ": actor " + std::to_string(k);
+        FI_REQUIRE(a, ak + " is null");
+        for (int j = 0; j < k; ++j) FI_REQUIRE(actors[j] != a, ak + " is actor " + std::to_string(j) + " again");
+        if (a->ro.T == 0) return fail(FI_ERR_STATE, ak + " does not record (fi_rollout_begin)");
+        auto differs = [&](const char* what, int actor, int learner) {
+            return fail(FI_ERR_INVALID, ak + "'s " + what + " " + std::to_string(actor) + " != the learner's " +
+                                            std::to_string(learner));
+        };
+        if (a->dev != li.dev) return differs("device", a->dev, li.dev);
+        if (a->cfg.arch != li.arch) return differs("arch", a->cfg.arch, li.arch);
+        if (a->A != li.A) return differs("num_actions", a->A, li.A);
+        if (li.arch == FI_ARCH_MLP && a->D != li.D) return differs("obs_dim", a->D, li.D);
+        if (a->ro.T != li.T) return differs("rollout seq_len", a->ro.T, li.T);
+        envs += a->N;
+    }
+    FI_REQUIRE(envs == li.B, nm + ": the actors' num_envs sum to " + std::to_string(envs) + " != the learner's batch " +
+                                 std::to_string(li.B));
+    FI_REQUIRE(li.dev_entries_ok, nm + ": an Atari handle reads device entries in the planes format only "
+                                       "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    for (int k = 0; k < n; ++k)
+        if (actors[k]->ro.ready < 0)
+            return fail(FI_ERR_STATE, nm + ": actor " + std::to_string(k) + " has no completed unroll (record " +
+                                          std::to_string(actors[k]->ro.t) + " of " +
+                                          std::to_string(actors[k]->ro.T + 1) + " is next); none was acquired");
+    fi_entry_segment segs[FI_MAX_SEGMENTS];
+    for (int k = 0; k < n; ++k) {
+        segs[k].num_entries = actors[k]->N;
+        FI_TRY(fi_rollout_acquire(actors[k], &segs[k].entries_dev, &segs[k].entry_stride, &segs[k].ready_event));
+    }
+    const int rc = wait ? fi_learner_step_segments_dev(l, segs, n, out) : fi_learner_step_segments_dev_async(l, segs, n);
+    // as fi_learner_step_rollout: the unrolls go back when the step ran (FI_ERR_NONFINITE: it ran and
+    // skipped its update) or, asynchronously, was enqueued -- the consumed event is recorded behind
+    // the ingest either way; after any other status they all stay
+    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
+    std::string why;
+    if (rc != FI_OK) why = fi_last_error();
+    for (int k = 0; k < n; ++k) FI_TRY(fi_rollout_release(actors[k], fi_learner_entries_consumed_event(l)));
+    return rc == FI_OK ? FI_OK : fail(rc, why);
+}
+
+extern "C" int fi_learner_step_rollouts(fi_learner* l, fi_actor* const* actors, int32_t n_actors, fi_step_stats* out) {
+    return step_rollouts(l, actors, n_actors, out, true, "step_rollouts");
+}
+
+extern "C" int fi_learner_step_rollouts_async(fi_learner* l, fi_actor* const* actors, int32_t n_actors) {
+    return step_rollouts(l, actors, n_actors, nullptr, false, "step_rollouts_async");
+}

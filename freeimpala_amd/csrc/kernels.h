@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fi_gather.h"
 #include "fi_learner.h"
 
 namespace fi {
@@ -94,6 +95,28 @@ int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entr
                                float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
                                int* bad = nullptr);
 
+// gather.hip: the same ingests with column b's entry at cols[b], a table of B base addresses in
+// device memory (include/fi_gather.h). The table is built on the device from segments that travel
+// as the kernel argument: segment k covers the columns [first, first + count), column c at
+// base + (c - first) * stride; the segments continue one another from column 0 to B.
+struct SegTable {
+    struct Seg {
+        const char* base;
+        size_t stride;
+        int32_t first, count;
+    } seg[FI_MAX_SEGMENTS];
+    int32_t n;
+};
+// versions (nullable, 16 bytes): set to {min = ~0, max = 0, sum = 0}, what the gathers below fold into
+int fill_columns_launch(const SegTable& tab, const void** cols, int B, uint32_t* versions, hipStream_t s);
+// versions (nullable): {min u32, max u32, sum u64} of the T * B records' flags words, by integer
+// atomics into the state fill_columns_launch leaves
+int gather_records_launch(const void* const* cols, int T, int B, int A, int D, float* obs, float* mu, int32_t* act,
+                          float* rew, float* disc, hipStream_t s, int* bad = nullptr, uint32_t* versions = nullptr);
+int gather_atari_planes_launch(const void* const* cols, int T, int B, int A, uint8_t* frames, float* mu, int32_t* act,
+                               float* rew, float* disc, hipStream_t s, int* bad = nullptr,
+                               uint32_t* versions = nullptr);
+
 // rollout.hip: one acting step into the learner's entry format (include/fi_rollout.h). logits ==
 // nullptr: the plane and episode_start (the observation) only
 int record_planes_launch(void* entries, size_t stride, int t, const uint8_t* planes, const uint8_t* start,
@@ -113,5 +136,25 @@ struct LearnerInfo {
     bool dev_entries_ok;  // MLP, or Atari in the planes format
 };
 int learner_info(const fi_learner* l, LearnerInfo* out);
+
+// learner.cpp: the step from segments (fi_gather.h). Its C entry points live in gather.hip and hand
+// in the ingest -- the column table, then the gathering launcher for the handle's policy -- so
+// learner.cpp names nothing of gather.hip either
+struct GatherTargets {
+    int arch, T, B, A, D;
+    float* obs;       // MLP
+    uint8_t* frames;  // Atari
+    float* mu;
+    int32_t* act;
+    float* rew;
+    float* disc;
+    int* bad;
+    const void** cols;   // B entry addresses
+    uint32_t* versions;  // behind the table
+    hipStream_t stream;
+};
+typedef int (*GatherIngestFn)(const SegTable& tab, const GatherTargets& to);
+int learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out, bool wait,
+                          const char* who, GatherIngestFn ingest);
 
 }  // namespace fi

@@ -97,6 +97,11 @@ struct fi_learner {
     int rec_format = FI_RECORDS_STACKED;  // Atari host entries: whole stacks, or single planes
     // entries already in device memory (fi_rollout.h): recorded after the ingest that read them
     hipEvent_t entries_consumed = nullptr;
+    // a batch gathered from segments (fi_gather.h): the column table, B base addresses, and behind
+    // it the version block {min u32, max u32, sum u64}; one allocation, on the first such step
+    const void** cols = nullptr;
+    uint32_t* versions = nullptr;
+    bool have_versions = false;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -601,7 +606,16 @@ struct DevEntries {
     hipEvent_t ready;
 };
 
-static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, const DevEntries* de = nullptr) {
+// entries in several device buffers, read through the column table (fi_learner_step_segments_dev)
+// `ingest` is gather.hip's (kernels.h): a library of the learner alone, without gather.hip, links
+struct GatherEntries {
+    SegTable tab;
+    hipEvent_t ready[FI_MAX_SEGMENTS];
+    GatherIngestFn ingest;
+};
+
+static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, const DevEntries* de = nullptr,
+                    const GatherEntries* ge = nullptr) {
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_a, l->stream));
@@ -619,6 +633,17 @@ static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, con
                                                   l->rew, l->disc, l->stream, l->bad));
         }
         FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
+    } else if (ge) {
+        for (int k = 0; k < ge->tab.n; ++k)
+            if (ge->ready[k]) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, ge->ready[k], 0));
+        {
+            Tag t(l, "ingest");
+            const GatherTargets gt{l->cfg.arch, l->T,   l->B,   l->A,    l->D,   l->obs,  l->frames,  l->mu,
+                                   l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
+            FI_TRY(ge->ingest(ge->tab, gt));
+        }
+        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
+        l->have_versions = true;
     } else if (have_host_batch) {
         const int s = l->cur;
         FI_HIP_CHECK(hipStreamWaitEvent(l->stream, l->h2d_done[s], 0));
@@ -928,12 +953,9 @@ extern "C" int fi_learner_wait(fi_learner* l, fi_step_stats* out) {
 }
 
 // ------------------------------------------------------------------ entries in device memory (fi_rollout.h)
-static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, const char* who) {
-    const std::string nm = who;
-    FI_REQUIRE(l && entries, nm + ": null argument");
-    FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
-               nm + ": an Atari handle reads device entries in the planes format only "
-                    "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+// n entries, `stride` apart, from `entries` on: the stride covers an entry, both are 16-byte aligned, and the
+// whole span is device memory of the handle's device inside one allocation
+static int check_entry_span(fi_learner* l, const void* entries, size_t stride, int n, const std::string& nm) {
     const size_t need = entry_bytes_min(l);
     FI_REQUIRE(stride >= need, nm + ": entry_stride " + std::to_string(stride) + " < " + std::to_string(need) +
                                    " = fi_learner_entry_bytes()");
@@ -952,10 +974,20 @@ static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, 
         (void)hipGetLastError();
         return fail(FI_ERR_INVALID, nm + ": entries_dev lies in no device allocation");
     }
-    const size_t span = (size_t)(l->B - 1) * stride + need;
+    const size_t span = (size_t)(n - 1) * stride + need;
     const size_t have = size - (size_t)((const char*)entries - (const char*)base);
     FI_REQUIRE(span <= have, nm + ": the allocation ends " + std::to_string(have) + " bytes behind entries_dev, " +
-                                 std::to_string(l->B) + " entries need " + std::to_string(span));
+                                 std::to_string(n) + " entries need " + std::to_string(span));
+    return FI_OK;
+}
+
+static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, const char* who) {
+    const std::string nm = who;
+    FI_REQUIRE(l && entries, nm + ": null argument");
+    FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
+               nm + ": an Atari handle reads device entries in the planes format only "
+                    "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    FI_TRY(check_entry_span(l, entries, stride, l->B, nm));
     if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
     return FI_OK;
 }
@@ -994,6 +1026,78 @@ extern "C" int fi_learner_step_entries_dev_async(fi_learner* l, const void* entr
 
 extern "C" void* fi_learner_entries_consumed_event(fi_learner* l) { return l ? (void*)l->entries_consumed : nullptr; }
 extern "C" size_t fi_learner_staging_bytes(const fi_learner* l) { return l ? 4 * l->rec_bytes : 0; }
+
+// ------------------------------------------------------------------ a batch gathered from segments (fi_gather.h)
+// The C entry points are gather.hip's: they pass its ingest in, so learner.cpp names none of its
+// launchers and a library of the learner alone still links (as with actor.hip above).
+int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out,
+                              bool wait, const char* who, GatherIngestFn ingest) {
+    try {
+        const std::string nm = who;
+        FI_REQUIRE(l && segs && ingest, nm + ": null argument");
+        FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
+                   nm + ": an Atari handle reads device entries in the planes format only "
+                        "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+        FI_REQUIRE(n_segs >= 1 && n_segs <= FI_MAX_SEGMENTS,
+                   nm + ": " + std::to_string(n_segs) + " segments, 1 .. " + std::to_string(FI_MAX_SEGMENTS) + " are taken");
+        GatherEntries ge{};
+        int64_t cols = 0;
+        for (int k = 0; k < n_segs; ++k) {
+            const std::string sk = nm + ": segment " + std::to_string(k);
+            FI_REQUIRE(segs[k].entries_dev, sk + ": null entries_dev");
+            FI_REQUIRE(segs[k].num_entries >= 1, sk + ": num_entries " + std::to_string(segs[k].num_entries) + " < 1");
+            FI_TRY(check_entry_span(l, segs[k].entries_dev, segs[k].entry_stride, segs[k].num_entries, sk));
+            FI_REQUIRE(cols + segs[k].num_entries <= l->B,
+                       sk + ": columns " + std::to_string(cols) + " .. " + std::to_string(cols + segs[k].num_entries) +
+                           " pass the learner's batch " + std::to_string(l->B));
+            ge.tab.seg[k] = {(const char*)segs[k].entries_dev, segs[k].entry_stride, (int32_t)cols, segs[k].num_entries};
+            ge.ready[k] = (hipEvent_t)segs[k].ready_event;
+            cols += segs[k].num_entries;
+        }
+        ge.tab.n = n_segs;
+        ge.ingest = ingest;
+        FI_REQUIRE(cols == l->B, nm + ": the segments hold " + std::to_string(cols) + " entries, the learner's batch is " +
+                                     std::to_string(l->B));
+        FI_HIP_CHECK(hipSetDevice(l->dev));
+        if (!l->cols) {
+            void* p = nullptr;
+            FI_TRY(dalloc(l, &p, 8 * (size_t)l->B + 16));
+            l->cols = (const void**)p;
+            l->versions = (uint32_t*)((char*)p + 8 * (size_t)l->B);
+        }
+        if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
+        if (!wait) {
+            FI_TRY(run_step(l, false, nullptr, nullptr, &ge));
+            l->in_flight = true;
+            return FI_OK;
+        }
+        l->in_flight = false;
+        FI_TRY(run_step(l, false, out, nullptr, &ge));
+        if (!out) {
+            FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+            FI_TRY(check_rejected(l));
+        }
+        return FI_OK;
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
+    }
+}
+
+extern "C" int fi_learner_batch_versions(fi_learner* l, fi_batch_versions* out) {
+    FI_REQUIRE(l && out, "batch_versions: null argument");
+    if (!l->have_versions)
+        return fail(FI_ERR_STATE, "batch_versions: no step from segments yet (fi_learner_step_segments_dev, "
+                                  "fi_learner_step_rollouts)");
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+    uint32_t h[4];
+    FI_HIP_CHECK(hipMemcpy(h, l->versions, sizeof(h), hipMemcpyDeviceToHost));
+    out->min_version = h[0];
+    out->max_version = h[1];
+    out->sum_versions = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+    out->count = (uint64_t)l->T * (uint64_t)l->B;
+    return FI_OK;
+}
 
 // what fi_learner_step_rollout (actor.hip: it needs both handles) compares with the actor
 int fi::learner_info(const fi_learner* l, LearnerInfo* out) {

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "fi_common.h"
+#include "interleave.h"
 #include "kernels.h"
 
 namespace fi {
@@ -250,17 +251,7 @@ static_assert(PLANE_REC == FI_ATARI_PLANE_RECORD_ELEMENTS * FI_RECORD_BYTES, "pl
 static_assert(3 * kPlaneBytes <= FI_ATARI_HISTORY_BYTES &&
                   FI_ATARI_HISTORY_BYTES == FI_ATARI_HISTORY_ELEMENTS * FI_RECORD_BYTES, "history block");
 
-// 4 pixels of channels 0..3 (one dword each) -> 4 NHWC pixels (byte c of a pixel = channel c)
-__device__ __forceinline__ uint4 interleave4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    const uint32_t ab_lo = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
-    const uint32_t ab_hi = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
-    const uint32_t cd_lo = __builtin_amdgcn_perm(d, c, 0x05010400u);
-    const uint32_t cd_hi = __builtin_amdgcn_perm(d, c, 0x07030602u);
-    return make_uint4(__builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u),   // a0 b0 c0 d0
-                      __builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u),   // a1 b1 c1 d1
-                      __builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u),
-                      __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u));
-}
+// interleave4 (4 pixels of channels 0..3 -> 4 NHWC pixels): interleave.h, shared with gather.hip
 
 __global__ __launch_bounds__(64) void ingest_planes_kernel(const char* __restrict__ rec, int T, int B,
                                                            size_t entry_bytes, uint4* __restrict__ frames) {

@@ -168,6 +168,41 @@ class DeviceLearner:
         from . import rollout
         return int(rollout.lib().fi_learner_staging_bytes(self._h))
 
+    # --- a batch gathered from several device buffers (include/fi_gather.h)
+    def step_rollouts(self, actors, stats: bool = True) -> dict:
+        """Acquire every actor's completed unroll, step from them in place (actor k fills the next
+        num_envs columns of the batch), release them all."""
+        from . import gather
+        st = _abi.StepStats()
+        check(gather.lib().fi_learner_step_rollouts(self._h, gather.actor_array(actors), len(actors),
+                                                    C.byref(st) if stats else None), "fi_learner_step_rollouts")
+        return st.as_dict() if stats else {}
+
+    def step_rollouts_async(self, actors) -> None:
+        """The same, enqueued only: the unrolls are released at once, see wait()."""
+        from . import gather
+        check(gather.lib().fi_learner_step_rollouts_async(self._h, gather.actor_array(actors), len(actors)),
+              "fi_learner_step_rollouts_async")
+
+    def step_segments_dev(self, segments, stats: bool = True) -> dict:
+        """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum
+        to the batch; segment k fills the next n columns once its event (or None) has completed."""
+        from . import gather
+        st = _abi.StepStats()
+        check(gather.lib().fi_learner_step_segments_dev(self._h, gather.segment_array(segments), len(segments),
+                                                        C.byref(st) if stats else None),
+              "fi_learner_step_segments_dev")
+        return st.as_dict() if stats else {}
+
+    @property
+    def batch_versions(self) -> dict:
+        """dict(min, max, mean, count) of the parameter versions (the records' flags words) in the
+        batch of the last step_rollouts / step_segments_dev."""
+        from . import gather
+        bv = gather.BatchVersions()
+        check(gather.lib().fi_learner_batch_versions(self._h, C.byref(bv)), "fi_learner_batch_versions")
+        return bv.as_dict()
+
     def synth(self, seed: int = 42, b_global: int = 0, b_offset: int = 0) -> None:
         check(lib().fi_learner_synth_batch(self._h, seed, b_global, b_offset), "synth")
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fi_actor.h"
+#include "fi_gather.h"
 #include "fi_rollout.h"
 
 namespace freeimpala_amd {
@@ -142,5 +143,16 @@ private:
     fi_actor* h_ = nullptr;
     std::string err_;
 };
+
+// Several recording actors fill one learner batch (include/fi_gather.h): actor k's completed unroll
+// becomes the next num_envs columns; the num_envs sum to the learner's batch. Acquire, step,
+// release in one call; the status is fi_learner_step_rollouts' (fi_last_error() has the message),
+// and after a refusal every unroll still waits.
+inline int step_rollouts(fi_learner* learner, const std::vector<DeviceActor*>& actors, fi_step_stats* stats) {
+    std::vector<fi_actor*> handles;
+    handles.reserve(actors.size());
+    for (DeviceActor* a : actors) handles.push_back(a ? a->handle() : nullptr);
+    return fi_learner_step_rollouts(learner, handles.data(), (int32_t)handles.size(), stats);
+}
 
 }  // namespace freeimpala_amd
