@@ -764,6 +764,13 @@ extern "C" int fi_rollout_end(fi_actor* a) {
     return FI_OK;
 }
 
+// what fi_ring_push_rollout (ring.hip) compares with the ring
+int fi::actor_info(const fi_actor* a, ActorInfo* out) {
+    FI_REQUIRE(a && out, "actor_info: null argument");
+    *out = ActorInfo{a->dev, a->N};
+    return FI_OK;
+}
+
 // acquire, step, release. It lives here, not in learner.cpp, because it holds both handles: the
 // learner is driven through its C ABI, and learner.cpp stays free of the actor.
 extern "C" int fi_learner_step_rollout(fi_learner* l, fi_actor* a, fi_step_stats* out) {

@@ -157,4 +157,18 @@ typedef int (*GatherIngestFn)(const SegTable& tab, const GatherTargets& to);
 int learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out, bool wait,
                           const char* who, GatherIngestFn ingest);
 
+// learner.cpp: the step from a source that writes the column table itself (fi_ring.h). ring.hip's C
+// entry points check the ring against learner_info() and hand in the ingest -- the columns kernel,
+// then the gathering launcher -- with ctx, the numbers of the batch; the learner's stream waits for
+// `ready` (nullable) first
+typedef int (*ColumnsIngestFn)(const void* ctx, const GatherTargets& to);
+int learner_step_columns(fi_learner* l, hipEvent_t ready, ColumnsIngestFn ingest, const void* ctx, fi_step_stats* out,
+                         bool wait, const char* who);
+
+// actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring
+struct ActorInfo {
+    int dev, N;
+};
+int actor_info(const fi_actor* a, ActorInfo* out);
+
 }  // namespace fi

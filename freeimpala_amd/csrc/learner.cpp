@@ -614,8 +614,21 @@ struct GatherEntries {
     GatherIngestFn ingest;
 };
 
+// entries of a source that writes the column table itself (fi_learner_step_ring: ring.hip hands in
+// `ingest`, its columns kernel and then the gathering launcher, and `ctx`, the numbers of the batch)
+struct ColumnEntries {
+    hipEvent_t ready;
+    ColumnsIngestFn ingest;
+    const void* ctx;
+};
+
+static GatherTargets gather_targets(const fi_learner* l) {
+    return GatherTargets{l->cfg.arch, l->T,   l->B,    l->A,   l->D,    l->obs,      l->frames, l->mu,
+                         l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
+}
+
 static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, const DevEntries* de = nullptr,
-                    const GatherEntries* ge = nullptr) {
+                    const GatherEntries* ge = nullptr, const ColumnEntries* ce = nullptr) {
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_a, l->stream));
@@ -638,9 +651,15 @@ static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, con
             if (ge->ready[k]) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, ge->ready[k], 0));
         {
             Tag t(l, "ingest");
-            const GatherTargets gt{l->cfg.arch, l->T,   l->B,   l->A,    l->D,   l->obs,  l->frames,  l->mu,
-                                   l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
-            FI_TRY(ge->ingest(ge->tab, gt));
+            FI_TRY(ge->ingest(ge->tab, gather_targets(l)));
+        }
+        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
+        l->have_versions = true;
+    } else if (ce) {
+        if (ce->ready) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, ce->ready, 0));
+        {
+            Tag t(l, "ingest");
+            FI_TRY(ce->ingest(ce->ctx, gather_targets(l)));
         }
         FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
         l->have_versions = true;
@@ -1030,6 +1049,30 @@ extern "C" size_t fi_learner_staging_bytes(const fi_learner* l) { return l ? 4 *
 // ------------------------------------------------------------------ a batch gathered from segments (fi_gather.h)
 // The C entry points are gather.hip's: they pass its ingest in, so learner.cpp names none of its
 // launchers and a library of the learner alone still links (as with actor.hip above).
+// the column table and the version block on first use, then the step, waited for or enqueued only
+static int step_gathered(fi_learner* l, const GatherEntries* ge, const ColumnEntries* ce, fi_step_stats* out, bool wait) {
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    if (!l->cols) {
+        void* p = nullptr;
+        FI_TRY(dalloc(l, &p, 8 * (size_t)l->B + 16));
+        l->cols = (const void**)p;
+        l->versions = (uint32_t*)((char*)p + 8 * (size_t)l->B);
+    }
+    if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
+    if (!wait) {
+        FI_TRY(run_step(l, false, nullptr, nullptr, ge, ce));
+        l->in_flight = true;
+        return FI_OK;
+    }
+    l->in_flight = false;
+    FI_TRY(run_step(l, false, out, nullptr, ge, ce));
+    if (!out) {
+        FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+        FI_TRY(check_rejected(l));
+    }
+    return FI_OK;
+}
+
 int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out,
                               bool wait, const char* who, GatherIngestFn ingest) {
     try {
@@ -1058,26 +1101,25 @@ int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32
         ge.ingest = ingest;
         FI_REQUIRE(cols == l->B, nm + ": the segments hold " + std::to_string(cols) + " entries, the learner's batch is " +
                                      std::to_string(l->B));
-        FI_HIP_CHECK(hipSetDevice(l->dev));
-        if (!l->cols) {
-            void* p = nullptr;
-            FI_TRY(dalloc(l, &p, 8 * (size_t)l->B + 16));
-            l->cols = (const void**)p;
-            l->versions = (uint32_t*)((char*)p + 8 * (size_t)l->B);
-        }
-        if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
-        if (!wait) {
-            FI_TRY(run_step(l, false, nullptr, nullptr, &ge));
-            l->in_flight = true;
-            return FI_OK;
-        }
-        l->in_flight = false;
-        FI_TRY(run_step(l, false, out, nullptr, &ge));
-        if (!out) {
-            FI_HIP_CHECK(hipStreamSynchronize(l->stream));
-            FI_TRY(check_rejected(l));
-        }
-        return FI_OK;
+        return step_gathered(l, &ge, nullptr, out, wait);
+    } catch (const std::exception& e) {
+        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
+    }
+}
+
+// ------------------------------------------------------------------ a batch chosen by a ring (fi_ring.h)
+// The C entry points are ring.hip's: it has checked the ring against learner_info() and passes in
+// the kernel that writes the column table, so learner.cpp names nothing of ring.hip.
+int fi::learner_step_columns(fi_learner* l, hipEvent_t ready, ColumnsIngestFn ingest, const void* ctx, fi_step_stats* out,
+                             bool wait, const char* who) {
+    try {
+        const std::string nm = who;
+        FI_REQUIRE(l && ingest, nm + ": null argument");
+        FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
+                   nm + ": an Atari handle reads device entries in the planes format only "
+                        "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+        const ColumnEntries ce{ready, ingest, ctx};
+        return step_gathered(l, nullptr, &ce, out, wait);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }

@@ -184,6 +184,20 @@ class DeviceLearner:
         check(gather.lib().fi_learner_step_rollouts_async(self._h, gather.actor_array(actors), len(actors)),
               "fi_learner_step_rollouts_async")
 
+    # --- a batch chosen from a device entry ring (include/fi_ring.h)
+    def step_ring(self, ring, n_fresh: int | None = None, wait: bool = True) -> dict | None:
+        """Step from an ``EntryRing``: the first n_fresh columns (default: all B, the reference's
+        readBatch(B)) take the oldest unread entries, the others are replayed from the entries read
+        before that are still resident. wait=False: enqueued only, see wait()."""
+        from . import ring as ring_mod
+        n = self.B if n_fresh is None else n_fresh
+        if not wait:
+            check(ring_mod.lib().fi_learner_step_ring_async(self._h, ring._h, n), "fi_learner_step_ring_async")
+            return None
+        st = _abi.StepStats()
+        check(ring_mod.lib().fi_learner_step_ring(self._h, ring._h, n, C.byref(st)), "fi_learner_step_ring")
+        return st.as_dict()
+
     def step_segments_dev(self, segments, stats: bool = True) -> dict:
         """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum
         to the batch; segment k fills the next n columns once its event (or None) has completed."""
