@@ -681,6 +681,7 @@ struct AtariImpl {
     bool fuse21 = true;    // conv2 backward + conv1 wgrad in one kernel (FI_BWD_UNFUSED=1 -> two)
     bool keep_da1 = false; // fused backward also stores da1 to HBM (FI_KEEP_DA1=1; parity checks)
     bool a1_planar = true; // fused fwd + bwd: a1 stored in conv21's image order (FI_A1_NHWC=1 -> NHWC)
+    bool fc_dg_ring = false; // fc dgrad on the LDS-ring kernel (FI_FC_DGRAD_RING=1; A/B and bit-identity tests)
     int fr_grid = 256;     // persistent frame-resident workgroups, 1 per CU (FI_FR_GRID=g: tests put
                            // many frames on each workgroup at small N to reach the steady state)
 };
@@ -739,6 +740,7 @@ AtariNet* atari_create(int B, int T, int A) {
     I->keep_da1 = std::getenv("FI_KEEP_DA1") != nullptr;
     // only conv21_bwd_fr reads a1 when both fused kernels run; every other consumer wants NHWC
     I->a1_planar = I->fr && I->fuse12 && I->fuse21 && std::getenv("FI_A1_NHWC") == nullptr;
+    I->fc_dg_ring = std::getenv("FI_FC_DGRAD_RING") != nullptr;
     if (const char* g = std::getenv("FI_FR_GRID")) I->fr_grid = std::max(1, std::min(256, std::atoi(g)));
     I->cs2 = (int)(((N * 100) + GBM - 1) / GBM * GBM);
     I->cs3 = (int)(((N * 81) + GBM - 1) / GBM * GBM);
@@ -874,7 +876,7 @@ int atari_backward(AtariNet* n, const uint8_t* frames, const float* dlogits, con
     // buckets in reverse layer order: fc + heads (95 % of the gradient bytes) reduce while
     // fc dgrad, conv3 and conv2/conv1 backward run
     if (gr && (rc = gr->ready(o.fcw, o.total - o.fcw))) return rc;
-    FI_A("fc_dgrad", fc_dgrad_launch(I->dh, I->wb.fcB, I->da3, I->fr ? Nb : N, s));  // the GEMM path reads all N
+    FI_A("fc_dgrad", fc_dgrad_launch(I->dh, I->wb.fcB, I->da3, I->fr ? Nb : N, s, I->fc_dg_ring));  // the GEMM path reads all N
     // conv3: wgrad [576][64] + bias, dgrad -> da2 (masked by a2)
     if (I->fr) {
         const int grid = std::min(N, I->fr_grid);

@@ -7,7 +7,10 @@
 //   dgrad    da3[R][3136] = dh[R][512] . fcW^T                           (K = 512)
 //   wgrad    dW[3136][512] = a3^T . dh  (reduction over R, split into fp32 slabs)
 //
-// Two kernels, both 512 threads (8 waves), 16x16x32 bf16 MFMA, fp32 accumulation. Operands
+// Three kernels, all 512 threads (8 waves), 16x16x32 bf16 MFMA, fp32 accumulation. The forward and
+// the weight gradient run the two ring kernels below; the data gradient runs fc_dgrad_wreg_kernel
+// (W in registers for the whole launch, only dh staged; described at the kernel), with the ring
+// kernel kept as its bit-identical baseline (FI_FC_DGRAD_RING=1). In the ring kernels operands
 // are staged by LDS-DMA (buffer_load_dwordx4 ... lds) into a ring of NS slots of BK k each;
 // step i waits (counted vmcnt) for its own slot and leaves the next NS-2 slots in flight
 // across the barrier, then issues step i+NS-1 into the slot step i-1 used (one barrier per
@@ -583,6 +586,116 @@ __global__ __launch_bounds__(512) void fc_tn_kernel(const __bf16* __restrict__ X
             __builtin_nontemporal_store(acc[f][g], (f32x4*)(out + (size_t)(yb + g * 16) * NXT + xb + f * 16));
 }
 
+// ---------------------------------------------------------------- dgrad, W in registers
+// da3[R][3136] = dh[R][512] . W^T with K = 512 short enough that a wave keeps its whole W slice
+// (32 da3 columns x 512 k: the MFMA's A fragments, 2 x 16 x 4 = 128 VGPRs) in registers for the
+// launch: loaded once with plain buffer loads, indexed by compile-time constants only. Only dh goes
+// through LDS: a slot is 64 rows x 512 k (64 KB), two slots; one 1-KiB DMA piece is one dh row,
+// its 16-B chunks XOR-swizzled with the row's low 4 bits on the DMA source (rows are 1 KiB apart,
+// i.e. on the same banks: the 16 lanes of a ds_read_b128 group then hit 16 distinct chunk
+// windows -- scripts/lds_conflicts.py, tests/test_fc_dgrad_map.py). Every wave reads the whole
+// slot: 4 row tiles x 16 k-steps = 64 ds_read_b128 for 128 MFMAs into 32 accumulator VGPRs, one
+// barrier per slot. Work map: work_map.h. W on the A side, dh on the B side, k ascending in steps
+// of 32 and the EpiDgrad::pair epilogue: bit-identical to fc_nt_kernel's dgrad. A slice is 512 B
+// wide and aligned, so every 128-B line of da3 is completed inside one workgroup. The stores of a
+// slot stay in flight across the next one (counted vmcnt). All global accesses go through buffer
+// descriptors that cover exactly W, the slot's rows of dh (rows past R read as zero) and the
+// slot's rows of da3 (rows past R are dropped).
+// OPT bits: 1 = s_setprio 1 on waves 4-7 for the whole kernel, 2 = non-temporal da3 stores, 4 = the next
+// slot's pieces issued half way through the slot instead of right after the barrier
+template <int OPT>
+__global__ __launch_bounds__(512) void fc_dgrad_wreg_kernel(const __bf16* __restrict__ dh, const __bf16* __restrict__ W,
+                                                            __bf16* __restrict__ da3, int R) {
+    constexpr int SR = kDgSlotRows, SLOT = SR * FCO * 2, PW = SR / 8, KS = FCO / 32, FY = SR / 16;
+    constexpr int AUX = (OPT & 2) ? 2 : 0;
+    static_assert(FCO * 2 == 1024 && PW * 8 == SR && kDgWaveCols == 32 && kDgSliceCols == 8 * kDgWaveCols, "slot");
+    static_assert((kDgSlices - 1) * kDgSliceCols < FCK && kDgSlices * kDgSliceCols >= FCK && FCK % kDgWaveCols == 0, "slices");
+    __shared__ __attribute__((aligned(16))) char lds[2 * SLOT];
+    const int lane = threadIdx.x & 63, w = wave_id(), G = lane >> 4, l15 = lane & 15;
+    const FcDgradMap m = fc_dgrad_map(blockIdx.x, R);
+    const int n = m.nslots > m.stream ? (m.nslots - 1 - m.stream) / kDgStreams + 1 : 0;  // this stream's slots
+    if (n == 0) return;
+    const int c0 = m.slice * kDgSliceCols + w * kDgWaveCols;  // this wave's da3 columns
+    const bool active = c0 < FCK;                             // wave-uniform (last slice: waves 0, 1)
+    if constexpr (OPT & 1) {
+        if (w >= 4) __builtin_amdgcn_s_setprio(1);
+    }
+    const uint32_t lbase = lds_addr(lds);
+
+    // W slice: wf[f][ks] = W[c0 + 16 f + l15][32 ks + 8 G ..+8] (an inactive wave's rows lie past
+    // the descriptor's range and read as zero)
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, FCK * FCO * 2, 0x00020000);
+    i32x4 wf[2][KS];
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            wf[f][ks] = __builtin_bit_cast(
+                i32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, ((c0 + 16 * f + l15) * FCO + 32 * ks + 8 * G) * 2, 0, 0));
+
+    auto issue = [&](int i) {  // this wave's 8 rows of the stream's slot i into LDS slot i & 1
+        const int row0 = (m.stream + i * kDgStreams) * SR;
+        const fi_i32x4 rd = make_rsrc(dh + (size_t)row0 * FCO, (uint32_t)min(SR, R - row0) * FCO * 2);
+        const uint32_t sb = lbase + (uint32_t)(i & 1) * SLOT;
+#pragma unroll
+        for (int p = 0; p < PW; ++p) {
+            const int row = w * PW + p;
+            dma16(rd, (uint32_t)(row * 1024 + ((lane ^ (row & 15)) << 4)), sb + (uint32_t)row * 1024u);
+        }
+    };
+    // B fragment of row tile g, k-step ks: row 16 g + l15, chunk (4 ks + G) ^ l15 -- four per-lane
+    // bases (ks & 3 meets the row's bits 2, 3), the rest compile-time offsets
+    int fb_off[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) fb_off[q] = l15 * 1024 + ((((q ^ (l15 >> 2)) << 2) | (G ^ (l15 & 3))) << 4);
+
+    issue(0);
+    // the W slice is complete before the loop (used here, so the loads are not sunk into it)
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(wf[f][ks]));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // ... and slot 0
+    for (int i = 0; i < n; ++i) {
+        // younger than slot i's pieces (issued after barrier i - 1): the stores of slot i - 1
+        if (i > 0) {
+            if (active) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FY) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        lds_barrier();
+        // into the slot every wave finished reading before this barrier
+        if (!(OPT & 4) || !active) {
+            if (i + 1 < n) issue(i + 1);
+        }
+        if (!active) continue;
+        const char* sb = lds + (i & 1) * SLOT;
+        f32x4 acc[2][FY];
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int g = 0; g < FY; ++g) acc[f][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            bf16x8 b[FY];
+            if constexpr ((OPT & 4) != 0) {
+                if (ks == KS / 2 && i + 1 < n) issue(i + 1);
+            }
+#pragma unroll
+            for (int g = 0; g < FY; ++g) b[g] = *(const bf16x8*)(sb + fb_off[ks & 3] + g * 16384 + (ks >> 2) * 256);
+#pragma unroll
+            for (int g = 0; g < FY; ++g)
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+                    acc[f][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[f][ks]), b[g], acc[f][g], 0, 0, 0);
+        }
+        const int row0 = (m.stream + i * kDgStreams) * SR;
+        const OutTile ot = EpiDgrad{{da3}}.tile(row0, min(SR, R - row0));
+#pragma unroll
+        for (int g = 0; g < FY; ++g)
+            EpiDgrad::template pair<AUX>(ot, nullptr, c0, row0 + g * 16 + l15, G, acc[0][g], acc[1][g]);
+    }
+}
+
 }  // namespace fcg
 
 #ifndef FI_FC_CONFIG_OVERRIDE
@@ -596,6 +709,8 @@ __global__ __launch_bounds__(512) void fc_tn_kernel(const __bf16* __restrict__ X
 // alone, 1.69 -> 1.64 ms in the step; 4.47 -> 3.96 GB of HBM traffic per launch; with default
 // stores 1.535-1.57 ms but 6.4 GB: the partial-line da3 writes are fetched first)
 #define FC_DG_CFG 224, 256, 1, 8, 64, 2, 1 | 2 | 128
+// the default dgrad is fc_dgrad_wreg_kernel (W in registers); its OPT bits
+#define FC_DGW_OPT 0
 // wgrad: x = dh columns (2 x 256), y = a3 columns (14 x 224), waves 4 x 2
 #define FC_WG_CFG 256, 224, 4, 2, 64, 2
 #endif
@@ -622,6 +737,14 @@ static int fc_dgrad_impl(const __bf16* dh, const __bf16* w, __bf16* da3, int row
     return FI_OK;
 }
 
+template <int OPT = 0>
+static int fc_dgrad_wreg_impl(const __bf16* dh, const __bf16* w, __bf16* da3, int rows, hipStream_t s) {
+    FI_REQUIRE(rows > 0, "fc_dgrad: rows must be positive");
+    hipLaunchKernelGGL((fc_dgrad_wreg_kernel<OPT>), dim3(kDgBlocks), dim3(512), 0, s, dh, w, da3, rows);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
 int fc_wgrad_splits(int rows) {
     // 28 output tiles; 9 R-slices -> 252 workgroups (one per CU); fewer for small R
     return std::max(1, std::min(9, (rows + 255) / 256));
@@ -642,8 +765,9 @@ static int fc_wgrad_impl(const __bf16* a3, const __bf16* dh, float* slab, float*
 int fc_fwd_launch(const __bf16* a3, const __bf16* wT, const float* bias, __bf16* h, int rows, hipStream_t s) {
     return fc_fwd_impl<FC_FW_CFG>(a3, wT, bias, h, rows, s);
 }
-int fc_dgrad_launch(const __bf16* dh, const __bf16* w, __bf16* da3, int rows, hipStream_t s) {
-    return fc_dgrad_impl<FC_DG_CFG>(dh, w, da3, rows, s);
+int fc_dgrad_launch(const __bf16* dh, const __bf16* w, __bf16* da3, int rows, hipStream_t s, bool ring) {
+    if (ring) return fc_dgrad_impl<FC_DG_CFG>(dh, w, da3, rows, s);
+    return fc_dgrad_wreg_impl<FC_DGW_OPT>(dh, w, da3, rows, s);
 }
 int fc_wgrad_launch(const __bf16* a3, const __bf16* dh, float* slab, float* dw, int rows, hipStream_t s) {
     return fc_wgrad_impl<FC_WG_CFG>(a3, dh, slab, dw, rows, s, fc_wgrad_splits(rows));

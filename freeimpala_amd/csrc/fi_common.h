@@ -7,6 +7,7 @@
 #include <string>
 
 #include "fi_learner.h"
+#include "work_map.h"  // xcd_remap
 
 namespace fi {
 
@@ -168,13 +169,6 @@ __device__ __forceinline__ uint32_t lds_addr(T* p) {
 
 __device__ __forceinline__ int wave_id() {
     return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-}
-
-// XCD-aware bijective remap (guide section 5, "XCD swizzle must be bijective"): blocks
-// that share an XCD (same bid % 8) get consecutive logical ids.
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
 template <typename T>

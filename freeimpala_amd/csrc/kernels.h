@@ -64,7 +64,9 @@ int f32_gemm_tn_wgrad(const float* dY, int M, int N, const float* X, int ldx, in
                       hipStream_t s);
 // fc_gemm.hip (the Atari fc layer, 3136 -> 512, rows = (T+1)*B)
 int fc_fwd_launch(const __bf16* a3, const __bf16* wT, const float* bias, __bf16* h, int rows, hipStream_t s);
-int fc_dgrad_launch(const __bf16* dh, const __bf16* w, __bf16* da3, int rows, hipStream_t s);  // da3 unmasked
+// da3 unmasked; ring: the LDS-ring kernel that stages both operands (the A/B baseline) instead of
+// the default with W in registers -- bit-identical results
+int fc_dgrad_launch(const __bf16* dh, const __bf16* w, __bf16* da3, int rows, hipStream_t s, bool ring = false);
 int fc_wgrad_splits(int rows);  // R-slices (fp32 slabs of 3136 x 512) fc_wgrad_launch uses
 int fc_wgrad_launch(const __bf16* a3, const __bf16* dh, float* slab, float* dw, int rows, hipStream_t s);
 int reduce_slabs(float* slab, int splits, size_t count, float* out, hipStream_t s);  // slab is scratch (overwritten)

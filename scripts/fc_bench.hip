@@ -6,6 +6,7 @@
 #define FI_FC_CONFIG_OVERRIDE
 #define FC_FW_CFG 256, 256, 4, 2, 64, 2, 8 | 4096
 #define FC_DG_CFG 224, 256, 1, 8, 64, 2, 1 | 2 | 128
+#define FC_DGW_OPT 0
 #define FC_WG_CFG 256, 224, 4, 2, 64, 2
 #include "../freeimpala_amd/csrc/fc_gemm.hip"
 
@@ -74,10 +75,19 @@ int main(int argc, char** argv) {
     };
 #define FWDV(nm, ...) add("fwd  " nm, 0, [&](hipStream_t st, int k) { return fc_fwd_impl<__VA_ARGS__>(a3, wT, bias, h[k], R, st); }, h[0], h[1], (size_t)R * FCO * 2)
 #define DGV(nm, ...) add("dgrd " nm, 1, [&](hipStream_t st, int k) { return fc_dgrad_impl<__VA_ARGS__>(dh, w, da3[k], R, st); }, da3[0], da3[1], (size_t)R * FCK * 2)
+#define DGW(nm, OPT) add("dgrd " nm, 1, [&](hipStream_t st, int k) { return fc_dgrad_wreg_impl<OPT>(dh, w, da3[k], R, st); }, da3[0], da3[1], (size_t)R * FCK * 2)
 #define WGV(nm, S, ...) add("wgrd " nm, 2, [&](hipStream_t st, int k) { return fc_wgrad_impl<__VA_ARGS__>(a3, dh, slab, dw[k], R, st, S); }, dw[0], dw[1], (size_t)FCK * FCO * 4)
-    // the shipped configurations first (fc_gemm.hip FC_*_CFG), then alternatives
+    // the forward and the ring dgrad as shipped (fc_gemm.hip FC_*_CFG; the ring is the bit-exact reference of its
+    // group), then alternatives
     FWDV("256x256 w4x2 bk64 ns2 ntY midbar", 256, 256, 4, 2, 64, 2, 8 | 4096);
     DGV("224x256 w1x8 bk64 ns2 prio ntst xrow", 224, 256, 1, 8, 64, 2, 1 | 2 | 128);
+    // W in registers, dh through LDS (fc_dgrad_wreg_kernel): store policy and s_setprio on waves 4-7
+    DGW("wreg 64x256 default stores", 0);
+    DGW("wreg 64x256 ntst", 2);
+    DGW("wreg 64x256 prio47", 1);
+    DGW("wreg 64x256 prio47 ntst", 1 | 2);
+    DGW("wreg 64x256 midissue", 4);
+    DGW("wreg 64x256 midissue prio47", 1 | 4);
     DGV("224x256 w1x8 bk64 ns2 prio ntst", 224, 256, 1, 8, 64, 2, 1 | 2);
     DGV("224x256 w1x8 bk64 ns2 prio xrow", 224, 256, 1, 8, 64, 2, 1 | 128);
     DGV("224x256 w1x8 bk64 ns2 prio", 224, 256, 1, 8, 64, 2, 1);

@@ -25,7 +25,7 @@ TAGS = {
         "conv21_bwd": ("conv21_bwd_fr", 1, 0), "conv12_fwd": ("conv12_fwd_fr", 1, 0),
         "conv3_bwd": ("conv3_bwd_fr", 1, 0), "conv3_fwd": ("conv_fwd_fr<3>", 1, 0),
         "vtrace": ("vtrace_lds_kernel", 1, 0), "fc_wgrad": ("fc_tn_kernel", 1, 0),
-        "fc_fwd": ("fcg::EpiFwd", 1, 0), "fc_dgrad": ("fcg::EpiDgrad", 1, 0),
+        "fc_fwd": ("fcg::EpiFwd", 1, 0), "fc_dgrad": (("fc_dgrad_wreg_kernel", "fcg::EpiDgrad"), 1, 0),
         "heads_fwd": ("EpiHeads", 1, 0), "heads_dgrad": ("heads_dgrad", 1, 0),
         "heads_wgrad": ("heads_wgrad", 1, 0),
     },
@@ -52,7 +52,7 @@ def pick(per, sub, period, phase):
     """values of every kernel name containing `sub`, every `period`-th dispatch from `phase`"""
     vals = []
     for n, vs in per.items():
-        if sub in n:
+        if any(x in n for x in ((sub,) if isinstance(sub, str) else sub)):
             vs = sorted(vs)
             vals += [v for j, (_, v) in enumerate(vs) if j % period == phase]
     return vals

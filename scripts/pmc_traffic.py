@@ -33,7 +33,7 @@ TAGS = {
         "conv21_bwd": ("conv21_bwd_fr", 1, 0),
         "fc_wgrad": ("fc_tn_kernel", 1, 0),
         "fc_fwd": ("fcg::EpiFwd", 1, 0),
-        "fc_dgrad": ("fcg::EpiDgrad", 1, 0),
+        "fc_dgrad": (("fc_dgrad_wreg_kernel", "fcg::EpiDgrad"), 1, 0),
         "heads_dgrad": ("heads_dgrad", 1, 0),
         "heads_wgrad": ("heads_wgrad", 1, 0),
         "heads_fwd": ("EpiHeads", 1, 0),
@@ -72,7 +72,7 @@ def read_counter(d, counter):
 def pick(per, sub, period, phase):
     vals = []
     for n, vs in per.items():
-        if sub in n:
+        if any(x in n for x in ((sub,) if isinstance(sub, str) else sub)):
             vals += [v for j, (_, v) in enumerate(vs) if j % period == phase]
     return vals
 
