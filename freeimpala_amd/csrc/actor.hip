@@ -25,6 +25,7 @@
 #include "fi_common.h"
 #include "fi_rollout.h"
 #include "kernels.h"
+#include "records.h"
 
 namespace fi {
 
@@ -32,7 +33,7 @@ namespace fi {
 // stacks[i] (84, 84, 4) u8 <- planes[i] (84, 84) u8, in place. A pixel is one dword of the stack
 // (byte c = channel c) and one byte p of the plane: the new dword is (w >> 8) | (p << 24) on a
 // shift and p * 0x01010101 on an episode start, one v_perm_b32 either way (interleave4's idiom,
-// misc.hip).
+// ingest_kernels.h).
 //   A one-wave workgroup owns an environment i and a run of 64 16-byte plane pieces (1,024
 // pixels = 256 16-byte stack pieces). Lane j loads plane piece 64 run + j; the wave turns the 256
 // plane dwords through LDS so that lane j holds dwords 64k + j (k = 0..3), the four pixels of
@@ -42,12 +43,9 @@ namespace fi {
 // array's own page) and a uniform branch -- a start does not read the stack. 7 runs cover the 441
 // plane pieces: the last has 57, and 228 = 3 * 64 + 36 stack pieces (the tail lanes are skipped).
 // 7 N workgroups, no grid cap. HBM traffic: (2 * 28,224 + 7,056) N bytes (a start: 28,224 fewer).
-constexpr int kPlaneBytes = 84 * 84;
-constexpr int kPlanePieces = kPlaneBytes / 16;        // 441
-constexpr int kPlaneRuns = (kPlanePieces + 63) / 64;  // 7
-constexpr int kStackBytes = 4 * kPlaneBytes;
-constexpr int kStackPieces = kStackBytes / 16;        // 1,764
-static_assert(kPlanePieces * 16 == kPlaneBytes && kStackPieces == 4 * kPlanePieces, "whole 16-byte pieces");
+// kPlaneBytes, kPlanePieces (441), kPlaneRuns (7): records.h; a stack is a frame
+constexpr int kStackBytes = kFrameBytes;
+constexpr int kStackPieces = kFramePieces;  // 1,764
 static_assert((size_t)kStackBytes == AtariNet::kFrameBytes, "a stack is one frame of the policy");
 
 // pixel q of plane dword n into the top byte of stack dword w, the rest one channel down
@@ -651,11 +649,11 @@ static int rollout_begin(fi_actor* a, int32_t T) {
     FI_REQUIRE(T >= 1 && T <= (1 << 20), "rollout_begin: seq_len must be >= 1");
     if (a->ro.T > 0) return fail(FI_ERR_STATE, "rollout_begin: the handle records already (fi_rollout_end first)");
     const bool atari = a->cfg.arch == FI_ARCH_ATARI;
-    FI_REQUIRE(!atari || a->A <= 18, "rollout_begin: the plane record's header holds mu[18]");
+    FI_REQUIRE(!atari || a->A <= kPlaneMaxActions, "rollout_begin: the plane record's header holds mu[18]");
     FI_HIP_CHECK(hipSetDevice(a->dev));
     auto& ro = a->ro;
-    ro.rec = atari ? (size_t)FI_ATARI_PLANE_RECORD_BYTES : (size_t)FI_RECORD_BYTES;
-    ro.entry = (size_t)(T + 1) * ro.rec + (atari ? (size_t)FI_ATARI_HISTORY_BYTES : 0);
+    ro.rec = atari ? (size_t)kPlaneRecBytes : (size_t)kMlpRecBytes;
+    ro.entry = (size_t)(T + 1) * ro.rec + (atari ? (size_t)kHistoryBytes : 0);
     const size_t bytes = (size_t)a->N * ro.entry;
     struct Guard {
         fi_actor* a;

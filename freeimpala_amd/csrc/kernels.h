@@ -83,24 +83,38 @@ int fill_hash_bf16(void* dst, size_t n, uint32_t seed, hipStream_t s);
 int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int D, float gamma,
                  float* obs, float* mu, int32_t* act, float* rew, float* disc, uint8_t* frames,
                  hipStream_t s);
-// actions outside [0, A) are counted into *bad (nullable) and stored clamped
-int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_bytes, float* obs,
-                  float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad = nullptr);
-// Atari records (FI_ATARI_RECORD_BYTES per step): frames (T+1, B, 84, 84, 4) u8 plus the same
-// header tensors; entry_bytes % 16 == 0, rec and frames 16-byte aligned
-int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
-                        float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
-                        int* bad = nullptr);
-// Atari plane records (FI_ATARI_PLANE_RECORD_BYTES per step, then the 3-plane history block): the
-// same outputs, the 4-frame stack rebuilt from single planes and episode_start; A <= 18
-int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
-                               float* mu, int32_t* act, float* rew, float* disc, hipStream_t s,
-                               int* bad = nullptr);
 
-// gather.hip: the same ingests with column b's entry at cols[b], a table of B base addresses in
-// device memory (include/fi_gather.h). The table is built on the device from segments that travel
-// as the kernel argument: segment k covers the columns [first, first + count), column c at
-// base + (c - first) * stride; the segments continue one another from column 0 to B.
+// The tensors an ingest fills: a learner's batch (learner.cpp) or the outputs a standalone entry
+// point names. Unused ones are nullptr.
+struct BatchTensors {
+    int arch, T, B, A, D;
+    float* obs;       // MLP
+    uint8_t* frames;  // Atari
+    float* mu;
+    int32_t* act;
+    float* rew;
+    float* disc;
+    int* bad;            // nullable: actions outside [0, A) are counted here (and stored clamped)
+    const void** cols;   // the gathering ingests: B entry addresses
+    uint32_t* versions;  // the gathering ingests, nullable: {min u32, max u32, sum u64} of the flags words
+    hipStream_t stream;
+};
+
+// misc.hip: B entries in one buffer, entry_bytes apart (ingest_kernels.h with the Strided locator;
+// record schemas: records.h). MLP records into obs / mu / act / rew / disc
+int ingest_launch(const void* rec, size_t entry_bytes, const BatchTensors& to);
+// stacked Atari records: frames (T+1, B, 84, 84, 4) u8 plus the same header tensors; entry_bytes
+// % 16 == 0, rec and frames 16-byte aligned
+int ingest_atari_launch(const void* rec, size_t entry_bytes, const BatchTensors& to);
+// Atari plane records, then the 3-plane history block: the same outputs, the 4-frame stack rebuilt
+// from single planes and episode_start; A <= 18
+int ingest_atari_planes_launch(const void* rec, size_t entry_bytes, const BatchTensors& to);
+
+// gather.hip: the same ingests with column b's entry at to.cols[b], a table of B base addresses in
+// device memory (include/fi_gather.h; ingest_kernels.h with the Table locator). The table is built
+// on the device from segments that travel as the kernel argument: segment k covers the columns
+// [first, first + count), column c at base + (c - first) * stride; the segments continue one
+// another from column 0 to B.
 struct SegTable {
     struct Seg {
         const char* base;
@@ -111,13 +125,12 @@ struct SegTable {
 };
 // versions (nullable, 16 bytes): set to {min = ~0, max = 0, sum = 0}, what the gathers below fold into
 int fill_columns_launch(const SegTable& tab, const void** cols, int B, uint32_t* versions, hipStream_t s);
-// versions (nullable): {min u32, max u32, sum u64} of the T * B records' flags words, by integer
-// atomics into the state fill_columns_launch leaves
-int gather_records_launch(const void* const* cols, int T, int B, int A, int D, float* obs, float* mu, int32_t* act,
-                          float* rew, float* disc, hipStream_t s, int* bad = nullptr, uint32_t* versions = nullptr);
-int gather_atari_planes_launch(const void* const* cols, int T, int B, int A, uint8_t* frames, float* mu, int32_t* act,
-                               float* rew, float* disc, hipStream_t s, int* bad = nullptr,
-                               uint32_t* versions = nullptr);
+// to.versions: by integer atomics into the state fill_columns_launch leaves
+int gather_records_launch(const BatchTensors& to);
+int gather_atari_planes_launch(const BatchTensors& to);
+// the gathering launcher for to.arch, behind a kernel that wrote to.cols: what a step from segments
+// and a step from a ring (ring.hip) both end their ingest in
+int gather_ingest(const BatchTensors& to);
 
 // rollout.hip: one acting step into the learner's entry format (include/fi_rollout.h). logits ==
 // nullptr: the plane and episode_start (the observation) only
@@ -127,8 +140,7 @@ int extract_history_launch(void* entries, size_t stride, size_t hist_off, const 
 int record_obs_launch(void* entries, size_t stride, int t, const float* obs, int D, const float* logits,
                       const int32_t* actions, uint32_t flags, int N, int A, hipStream_t s);
 // out: N rewards then N discounts; field: byte offset of the reward in entry 0 (the record's
-// offset plus the reward's in a record: the discount follows it)
-constexpr size_t kPlaneRecReward = 7132, kMlpRecReward = 772;
+// offset plus the reward's in a record, records.h: the discount follows it)
 int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* out, int N, hipStream_t s);
 
 // learner.cpp: what fi_learner_step_rollout (actor.hip: it holds both handles) compares with the
@@ -139,32 +151,16 @@ struct LearnerInfo {
 };
 int learner_info(const fi_learner* l, LearnerInfo* out);
 
-// learner.cpp: the step from segments (fi_gather.h). Its C entry points live in gather.hip and hand
-// in the ingest -- the column table, then the gathering launcher for the handle's policy -- so
-// learner.cpp names nothing of gather.hip either
-struct GatherTargets {
-    int arch, T, B, A, D;
-    float* obs;       // MLP
-    uint8_t* frames;  // Atari
-    float* mu;
-    int32_t* act;
-    float* rew;
-    float* disc;
-    int* bad;
-    const void** cols;   // B entry addresses
-    uint32_t* versions;  // behind the table
-    hipStream_t stream;
-};
-typedef int (*GatherIngestFn)(const SegTable& tab, const GatherTargets& to);
+// learner.cpp: a step's batch source, for the C entry points that live outside it. `ingest` fills the
+// learner's tensors from what ctx names; gather.hip and ring.hip hand theirs in, so learner.cpp names
+// nothing of either and a library of the learner alone links.
+typedef int (*IngestFn)(const void* ctx, const BatchTensors& to);
+// the step from segments (fi_gather.h): the checks of the segments, then ingest(&SegTable, tensors)
 int learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out, bool wait,
-                          const char* who, GatherIngestFn ingest);
-
-// learner.cpp: the step from a source that writes the column table itself (fi_ring.h). ring.hip's C
-// entry points check the ring against learner_info() and hand in the ingest -- the columns kernel,
-// then the gathering launcher -- with ctx, the numbers of the batch; the learner's stream waits for
-// `ready` (nullable) first
-typedef int (*ColumnsIngestFn)(const void* ctx, const GatherTargets& to);
-int learner_step_columns(fi_learner* l, hipEvent_t ready, ColumnsIngestFn ingest, const void* ctx, fi_step_stats* out,
+                          const char* who, IngestFn ingest);
+// the step from a source that writes the column table itself (fi_ring.h: ring.hip has checked the
+// ring against learner_info()); the learner's stream waits for `ready` (nullable) first
+int learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
                          bool wait, const char* who);
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring

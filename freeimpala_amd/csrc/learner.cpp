@@ -89,7 +89,7 @@ struct fi_learner {
     hipEvent_t ingest_done[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr;
     int stage = 0;
-    int cur = 0;             // slot the next run_step ingests from
+    int cur = 0;             // slot the next host step ingests from
     int acquired = -1;       // slot handed out by acquire_slot and not yet submitted
     bool in_flight = false;  // an async step was enqueued and not yet waited for
     size_t rec_bytes = 0;
@@ -599,92 +599,39 @@ static void fill_stats(fi_learner* l, fi_step_stats* out) {
     out->step_ms = 0.f;
 }
 
-// entries in device memory, read in place by the ingest (fi_learner_step_entries_dev)
-struct DevEntries {
-    const void* ptr;
-    size_t stride;
-    hipEvent_t ready;
-};
-
-// entries in several device buffers, read through the column table (fi_learner_step_segments_dev)
-// `ingest` is gather.hip's (kernels.h): a library of the learner alone, without gather.hip, links
-struct GatherEntries {
-    SegTable tab;
-    hipEvent_t ready[FI_MAX_SEGMENTS];
-    GatherIngestFn ingest;
-};
-
-// entries of a source that writes the column table itself (fi_learner_step_ring: ring.hip hands in
-// `ingest`, its columns kernel and then the gathering launcher, and `ctx`, the numbers of the batch)
-struct ColumnEntries {
-    hipEvent_t ready;
-    ColumnsIngestFn ingest;
+// Where a step's batch comes from; nullptr = the resident batch (fi_learner_step_resident, the
+// synthetic one). `ingest` is a plain function and `ctx` what it reads: nothing is allocated per
+// step, and gather.hip's and ring.hip's ingests arrive as pointers (kernels.h), so a library of the
+// learner alone, without them, links.
+struct BatchSource {
+    const hipEvent_t* wait;  // the learner's stream waits for these first (null entries are skipped)
+    int n_wait;
+    IngestFn ingest;
     const void* ctx;
+    hipEvent_t done;  // recorded behind the ingest: ingest_done[slot], or entries_consumed
+    bool versions;    // the ingest fills the version block
 };
 
-static GatherTargets gather_targets(const fi_learner* l) {
-    return GatherTargets{l->cfg.arch, l->T,   l->B,    l->A,   l->D,    l->obs,      l->frames, l->mu,
-                         l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
+static BatchTensors batch_tensors(const fi_learner* l) {
+    return BatchTensors{l->cfg.arch, l->T,   l->B,    l->A,   l->D,    l->obs,      l->frames, l->mu,
+                        l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
 }
 
-static int run_step(fi_learner* l, bool have_host_batch, fi_step_stats* out, const DevEntries* de = nullptr,
-                    const GatherEntries* ge = nullptr, const ColumnEntries* ce = nullptr) {
+static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_a, l->stream));
     mark(l, FI_PHASE_INGEST);
     FI_HIP_CHECK(hipMemsetAsync(l->bad, 0, sizeof(int), l->stream));
-    if (de) {
-        if (de->ready) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, de->ready, 0));
+    if (src) {
+        for (int k = 0; k < src->n_wait; ++k)
+            if (src->wait[k]) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, src->wait[k], 0));
         {
             Tag t(l, "ingest");
-            if (l->cfg.arch == FI_ARCH_MLP)
-                FI_TRY(ingest_launch(de->ptr, l->T, l->B, l->A, l->D, de->stride, l->obs, l->mu, l->act, l->rew,
-                                     l->disc, l->stream, l->bad));
-            else
-                FI_TRY(ingest_atari_planes_launch(de->ptr, l->T, l->B, l->A, de->stride, l->frames, l->mu, l->act,
-                                                  l->rew, l->disc, l->stream, l->bad));
+            FI_TRY(src->ingest(src->ctx, batch_tensors(l)));
         }
-        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
-    } else if (ge) {
-        for (int k = 0; k < ge->tab.n; ++k)
-            if (ge->ready[k]) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, ge->ready[k], 0));
-        {
-            Tag t(l, "ingest");
-            FI_TRY(ge->ingest(ge->tab, gather_targets(l)));
-        }
-        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
-        l->have_versions = true;
-    } else if (ce) {
-        if (ce->ready) FI_HIP_CHECK(hipStreamWaitEvent(l->stream, ce->ready, 0));
-        {
-            Tag t(l, "ingest");
-            FI_TRY(ce->ingest(ce->ctx, gather_targets(l)));
-        }
-        FI_HIP_CHECK(hipEventRecord(l->entries_consumed, l->stream));
-        l->have_versions = true;
-    } else if (have_host_batch) {
-        const int s = l->cur;
-        FI_HIP_CHECK(hipStreamWaitEvent(l->stream, l->h2d_done[s], 0));
-        {
-            Tag t(l, "ingest");
-            if (l->cfg.arch == FI_ARCH_MLP)
-                FI_TRY(ingest_launch(l->rec_slot[s], l->T, l->B, l->A, l->D, l->rec_entry_bytes, l->obs,
-                                     l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
-            else if (l->rec_format == FI_RECORDS_PLANES)
-                FI_TRY(ingest_atari_planes_launch(l->rec_slot[s], l->T, l->B, l->A, l->rec_entry_bytes,
-                                                  l->frames, l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
-            else
-                // frames (like mu / act / rew / disc) is rewritten in place: every kernel that
-                // read it in the previous step -- the forward and the backward's conv1 weight
-                // gradient -- was enqueued on this same stream, so stream order puts them before
-                // the ingest. The only other stream with work of the previous step, comm_stream,
-                // touches grads and the reject flag alone, and was joined before that step's
-                // optimizer (BucketAllReduce::join).
-                FI_TRY(ingest_atari_launch(l->rec_slot[s], l->T, l->B, l->A, l->rec_entry_bytes,
-                                           l->frames, l->mu, l->act, l->rew, l->disc, l->stream, l->bad));
-        }
-        FI_HIP_CHECK(hipEventRecord(l->ingest_done[s], l->stream));
+        FI_HIP_CHECK(hipEventRecord(src->done, l->stream));
+        if (src->versions) l->have_versions = true;
     }
     mark(l, FI_PHASE_FORWARD);
     if (l->cfg.arch == FI_ARCH_MLP) FI_TRY(mlp_forward(l));
@@ -766,7 +713,7 @@ extern "C" int fi_learner_step_resident(fi_learner* l, fi_step_stats* out) {
     FI_REQUIRE(l, "step: null learner");
     FI_HIP_CHECK(hipSetDevice(l->dev));
     try {
-        return run_step(l, false, out);
+        return run_step(l, nullptr, out);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string("step: ") + e.what());
     }
@@ -889,10 +836,17 @@ static int stage_entries(fi_learner* l, const void* const* entries, size_t n_ent
     return submit_slot(l);
 }
 
-// a synchronous step: returns when the device step has completed, statistics or not
-static int step_and_wait(fi_learner* l, fi_step_stats* out) {
+// Runs the step from `src` and ends it. wait: returns when the device step has completed,
+// statistics or not, and reports a batch it rejected; otherwise the step is enqueued only (no
+// sync) and fi_learner_wait reports it.
+static int finish_step(fi_learner* l, const BatchSource& src, fi_step_stats* out, bool wait) {
+    if (!wait) {
+        FI_TRY(run_step(l, &src, nullptr));
+        l->in_flight = true;
+        return FI_OK;
+    }
     l->in_flight = false;
-    FI_TRY(run_step(l, true, out));
+    FI_TRY(run_step(l, &src, out));
     if (!out) {
         FI_HIP_CHECK(hipStreamSynchronize(l->stream));
         FI_TRY(check_rejected(l));
@@ -900,11 +854,36 @@ static int step_and_wait(fi_learner* l, fi_step_stats* out) {
     return FI_OK;
 }
 
+// the contiguous ingests (misc.hip): ctx names the entries
+struct Entries {
+    const void* ptr;
+    size_t stride;
+    int format;  // Atari: FI_RECORDS_*
+};
+static int ingest_entries(const void* ctx, const BatchTensors& to) {
+    const Entries& e = *(const Entries*)ctx;
+    if (to.arch == FI_ARCH_MLP) return ingest_launch(e.ptr, e.stride, to);
+    if (e.format == FI_RECORDS_PLANES) return ingest_atari_planes_launch(e.ptr, e.stride, to);
+    // frames (like mu / act / rew / disc) is rewritten in place: every kernel that read it in the
+    // previous step -- the forward and the backward's conv1 weight gradient -- was enqueued on
+    // this same stream, so stream order puts them before the ingest. The only other stream with
+    // work of the previous step, comm_stream, touches grads and the reject flag alone, and was
+    // joined before that step's optimizer (BucketAllReduce::join).
+    return ingest_atari_launch(e.ptr, e.stride, to);
+}
+
+// the step from the staged host batch in device slot l->cur
+static int step_staged_slot(fi_learner* l, fi_step_stats* out, bool wait) {
+    const int s = l->cur;
+    const Entries e{l->rec_slot[s], l->rec_entry_bytes, l->rec_format};
+    return finish_step(l, BatchSource{&l->h2d_done[s], 1, ingest_entries, &e, l->ingest_done[s], false}, out, wait);
+}
+
 extern "C" int fi_learner_step(fi_learner* l, const void* const* entries, size_t n_entries,
                                size_t entry_bytes, fi_step_stats* out) {
     try {
         FI_TRY(stage_entries(l, entries, n_entries, entry_bytes));
-        return step_and_wait(l, out);
+        return step_staged_slot(l, out, true);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string("step: ") + e.what());
     }
@@ -914,9 +893,7 @@ extern "C" int fi_learner_step_async(fi_learner* l, const void* const* entries, 
                                      size_t entry_bytes) {
     try {
         FI_TRY(stage_entries(l, entries, n_entries, entry_bytes));
-        FI_TRY(run_step(l, true, nullptr));  // enqueued only (no stats requested: no sync)
-        l->in_flight = true;
-        return FI_OK;
+        return step_staged_slot(l, nullptr, false);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string("step_async: ") + e.what());
     }
@@ -941,7 +918,7 @@ extern "C" int fi_learner_step_staged(fi_learner* l, fi_step_stats* out) {
     try {
         FI_HIP_CHECK(hipSetDevice(l->dev));
         FI_TRY(submit_slot(l));
-        return step_and_wait(l, out);
+        return step_staged_slot(l, out, true);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string("step_staged: ") + e.what());
     }
@@ -952,9 +929,7 @@ extern "C" int fi_learner_step_staged_async(fi_learner* l) {
     try {
         FI_HIP_CHECK(hipSetDevice(l->dev));
         FI_TRY(submit_slot(l));
-        FI_TRY(run_step(l, true, nullptr));
-        l->in_flight = true;
-        return FI_OK;
+        return step_staged_slot(l, nullptr, false);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string("step_staged_async: ") + e.what());
     }
@@ -1000,13 +975,18 @@ static int check_entry_span(fi_learner* l, const void* entries, size_t stride, i
     return FI_OK;
 }
 
-static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, const char* who) {
-    const std::string nm = who;
-    FI_REQUIRE(l && entries, nm + ": null argument");
-    FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
-               nm + ": an Atari handle reads device entries in the planes format only "
-                    "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
-    FI_TRY(check_entry_span(l, entries, stride, l->B, nm));
+// an Atari handle reads device entries in the planes format only (the stacked one is a host format)
+static bool dev_entries_ok(const fi_learner* l) {
+    return l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES;
+}
+static int require_dev_entries(const fi_learner* l, const std::string& nm) {
+    FI_REQUIRE(dev_entries_ok(l), nm + ": an Atari handle reads device entries in the planes format only "
+                                       "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    return FI_OK;
+}
+
+// entries_consumed, created by the first step from device entries
+static int ensure_entries_consumed(fi_learner* l) {
     if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
     return FI_OK;
 }
@@ -1014,20 +994,14 @@ static int check_dev_entries(fi_learner* l, const void* entries, size_t stride, 
 static int step_entries_dev(fi_learner* l, const void* entries, size_t stride, void* ready, fi_step_stats* out,
                             bool wait, const char* who) {
     try {
-        FI_TRY(check_dev_entries(l, entries, stride, who));
-        const DevEntries de{entries, stride, (hipEvent_t)ready};
-        if (!wait) {
-            FI_TRY(run_step(l, false, nullptr, &de));
-            l->in_flight = true;
-            return FI_OK;
-        }
-        l->in_flight = false;
-        FI_TRY(run_step(l, false, out, &de));
-        if (!out) {
-            FI_HIP_CHECK(hipStreamSynchronize(l->stream));
-            FI_TRY(check_rejected(l));
-        }
-        return FI_OK;
+        const std::string nm = who;
+        FI_REQUIRE(l && entries, nm + ": null argument");
+        FI_TRY(require_dev_entries(l, nm));
+        FI_TRY(check_entry_span(l, entries, stride, l->B, nm));
+        FI_TRY(ensure_entries_consumed(l));
+        const hipEvent_t ev = (hipEvent_t)ready;
+        const Entries e{entries, stride, l->rec_format};
+        return finish_step(l, BatchSource{&ev, 1, ingest_entries, &e, l->entries_consumed, false}, out, wait);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }
@@ -1046,11 +1020,13 @@ extern "C" int fi_learner_step_entries_dev_async(fi_learner* l, const void* entr
 extern "C" void* fi_learner_entries_consumed_event(fi_learner* l) { return l ? (void*)l->entries_consumed : nullptr; }
 extern "C" size_t fi_learner_staging_bytes(const fi_learner* l) { return l ? 4 * l->rec_bytes : 0; }
 
-// ------------------------------------------------------------------ a batch gathered from segments (fi_gather.h)
-// The C entry points are gather.hip's: they pass its ingest in, so learner.cpp names none of its
-// launchers and a library of the learner alone still links (as with actor.hip above).
+// ------------------------------------------------------------------ a batch read through the column table
+// (fi_gather.h, fi_ring.h). The C entry points are gather.hip's and ring.hip's: they pass their
+// ingest in, so learner.cpp names none of their launchers and a library of the learner alone
+// still links (as with actor.hip above).
 // the column table and the version block on first use, then the step, waited for or enqueued only
-static int step_gathered(fi_learner* l, const GatherEntries* ge, const ColumnEntries* ce, fi_step_stats* out, bool wait) {
+static int step_gathered(fi_learner* l, const hipEvent_t* ready, int n_ready, IngestFn ingest, const void* ctx,
+                         fi_step_stats* out, bool wait) {
     FI_HIP_CHECK(hipSetDevice(l->dev));
     if (!l->cols) {
         void* p = nullptr;
@@ -1058,32 +1034,20 @@ static int step_gathered(fi_learner* l, const GatherEntries* ge, const ColumnEnt
         l->cols = (const void**)p;
         l->versions = (uint32_t*)((char*)p + 8 * (size_t)l->B);
     }
-    if (!l->entries_consumed) FI_HIP_CHECK(hipEventCreateWithFlags(&l->entries_consumed, hipEventDisableTiming));
-    if (!wait) {
-        FI_TRY(run_step(l, false, nullptr, nullptr, ge, ce));
-        l->in_flight = true;
-        return FI_OK;
-    }
-    l->in_flight = false;
-    FI_TRY(run_step(l, false, out, nullptr, ge, ce));
-    if (!out) {
-        FI_HIP_CHECK(hipStreamSynchronize(l->stream));
-        FI_TRY(check_rejected(l));
-    }
-    return FI_OK;
+    FI_TRY(ensure_entries_consumed(l));
+    return finish_step(l, BatchSource{ready, n_ready, ingest, ctx, l->entries_consumed, true}, out, wait);
 }
 
 int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out,
-                              bool wait, const char* who, GatherIngestFn ingest) {
+                              bool wait, const char* who, IngestFn ingest) {
     try {
         const std::string nm = who;
         FI_REQUIRE(l && segs && ingest, nm + ": null argument");
-        FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
-                   nm + ": an Atari handle reads device entries in the planes format only "
-                        "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+        FI_TRY(require_dev_entries(l, nm));
         FI_REQUIRE(n_segs >= 1 && n_segs <= FI_MAX_SEGMENTS,
                    nm + ": " + std::to_string(n_segs) + " segments, 1 .. " + std::to_string(FI_MAX_SEGMENTS) + " are taken");
-        GatherEntries ge{};
+        SegTable tab{};
+        hipEvent_t ready[FI_MAX_SEGMENTS];
         int64_t cols = 0;
         for (int k = 0; k < n_segs; ++k) {
             const std::string sk = nm + ": segment " + std::to_string(k);
@@ -1093,33 +1057,26 @@ int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32
             FI_REQUIRE(cols + segs[k].num_entries <= l->B,
                        sk + ": columns " + std::to_string(cols) + " .. " + std::to_string(cols + segs[k].num_entries) +
                            " pass the learner's batch " + std::to_string(l->B));
-            ge.tab.seg[k] = {(const char*)segs[k].entries_dev, segs[k].entry_stride, (int32_t)cols, segs[k].num_entries};
-            ge.ready[k] = (hipEvent_t)segs[k].ready_event;
+            tab.seg[k] = {(const char*)segs[k].entries_dev, segs[k].entry_stride, (int32_t)cols, segs[k].num_entries};
+            ready[k] = (hipEvent_t)segs[k].ready_event;
             cols += segs[k].num_entries;
         }
-        ge.tab.n = n_segs;
-        ge.ingest = ingest;
+        tab.n = n_segs;
         FI_REQUIRE(cols == l->B, nm + ": the segments hold " + std::to_string(cols) + " entries, the learner's batch is " +
                                      std::to_string(l->B));
-        return step_gathered(l, &ge, nullptr, out, wait);
+        return step_gathered(l, ready, n_segs, ingest, &tab, out, wait);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }
 }
 
-// ------------------------------------------------------------------ a batch chosen by a ring (fi_ring.h)
-// The C entry points are ring.hip's: it has checked the ring against learner_info() and passes in
-// the kernel that writes the column table, so learner.cpp names nothing of ring.hip.
-int fi::learner_step_columns(fi_learner* l, hipEvent_t ready, ColumnsIngestFn ingest, const void* ctx, fi_step_stats* out,
+int fi::learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
                              bool wait, const char* who) {
     try {
         const std::string nm = who;
         FI_REQUIRE(l && ingest, nm + ": null argument");
-        FI_REQUIRE(l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES,
-                   nm + ": an Atari handle reads device entries in the planes format only "
-                        "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
-        const ColumnEntries ce{ready, ingest, ctx};
-        return step_gathered(l, nullptr, &ce, out, wait);
+        FI_TRY(require_dev_entries(l, nm));
+        return step_gathered(l, &ready, 1, ingest, ctx, out, wait);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }
@@ -1144,8 +1101,7 @@ extern "C" int fi_learner_batch_versions(fi_learner* l, fi_batch_versions* out) 
 // what fi_learner_step_rollout (actor.hip: it needs both handles) compares with the actor
 int fi::learner_info(const fi_learner* l, LearnerInfo* out) {
     FI_REQUIRE(l && out, "learner_info: null argument");
-    *out = LearnerInfo{l->dev, l->cfg.arch, l->B, l->A, l->D, l->T,
-                       l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES};
+    *out = LearnerInfo{l->dev, l->cfg.arch, l->B, l->A, l->D, l->T, dev_entries_ok(l)};
     return FI_OK;
 }
 

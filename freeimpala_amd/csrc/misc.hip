@@ -2,13 +2,13 @@
 //   * synthetic trajectories (Philox4x32-10, bit-identical to the oracle's generator)
 //   * ingest: (B, S*1024) SharedBuffer entries -> time-major SoA tensors (MLP records, the
 //     Atari records with their 84x84x4 frames, and the single-plane Atari records whose
-//     4-frame stack is rebuilt here)
+//     4-frame stack is rebuilt): the kernels of ingest_kernels.h on entries a fixed stride apart
 //   * column sums / split-K slab reduction (deterministic, fixed order)
 //   * global gradient norm, Adam / SGD with global-norm clipping, fp32 -> bf16
 #include <algorithm>
 
 #include "fi_common.h"
-#include "interleave.h"
+#include "ingest_kernels.h"
 #include "kernels.h"
 
 namespace fi {
@@ -69,11 +69,7 @@ __global__ void synth_frames_kernel(uint64_t seed, int rows, int B, int B_glob, 
     }
 }
 
-static int grid_for(size_t n) {
-    size_t g = (n + 255) / 256;
-    return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
+// grid_for: ingest_kernels.h
 int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int D, float gamma,
                  float* obs, float* mu, int32_t* act, float* rew, float* disc, uint8_t* frames,
                  hipStream_t s) {
@@ -97,60 +93,10 @@ int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int 
 }
 
 // ---------------------------------------------------------------- ingest
-// MLP record schema (one 1 KiB ELEMENT per step, reference data_structures.h:35, agent.h:62):
-//   [0,512) float obs[<=128] | [512,768) float mu_logits[<=64] | 768 int32 action |
-//   772 float reward | 776 float discount | 780 uint32 flags | 784.. reserved.
-// Atari record schema (28 ELEMENTs = 28,672 B per step, FI_ATARI_RECORD_BYTES):
-//   [0,28224) u8 frame 84x84x4 NHWC | [28224,28480) float mu_logits[<=64] | 28480 int32 action |
-//   28484 float reward | 28488 float discount | 28492 uint32 flags | 28496.. reserved.
-// Both headers have the same shape: mu, then action / reward / discount at +256 / +260 / +264.
-// An entry holds T+1 records (record T = bootstrap observation; its header is ignored).
-// Atari plane record schema (7 ELEMENTs = 7,168 B per step, FI_ATARI_PLANE_RECORD_BYTES):
-//   [0,7056) u8 plane 84x84 (the newest observation) | [7056,7128) float mu_logits[<=18] |
-//   7128 int32 action | 7132 float reward | 7136 float discount | 7140 uint32 flags |
-//   7144 uint32 episode_start | 7148.. reserved.
-// Its entry holds T+1 records and then, at (T+1)*7168, the three planes that precede record 0 in
-// the actor's stack (oldest first, 3*7056 B, padded to FI_ATARI_HISTORY_BYTES).
-constexpr int REC_OBS = 0, REC_MU = 512;
-constexpr int HDR_ACT = 256;  // relative to the record's mu; reward and discount follow the action
-constexpr int kFrameBytes = 84 * 84 * 4;
-constexpr int kFramePieces = kFrameBytes / 16;  // 1,764 16-byte pieces
-constexpr int ATARI_REC_MU = kFrameBytes;
-static_assert(ATARI_REC_MU + HDR_ACT + 16 <= FI_ATARI_RECORD_BYTES, "Atari record header");
-static_assert(FI_ATARI_RECORD_BYTES == FI_ATARI_RECORD_ELEMENTS * FI_RECORD_BYTES, "Atari record size");
+// Entries in one buffer, entry_bytes apart: the kernels of ingest_kernels.h with the Strided
+// locator (no version block on this path: the flags word is not loaded). Record schemas: records.h.
 
-__global__ void ingest_vec_kernel(const char* __restrict__ rec, int rows, int B, int W,
-                                  int rec_off, size_t rec_stride, size_t entry_bytes,
-                                  float* __restrict__ out) {
-    const size_t n = (size_t)rows * B * W;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const size_t lrow = i / W;
-        const int d = (int)(i - lrow * W);
-        const int t = (int)(lrow / B), b = (int)(lrow - (size_t)t * B);
-        out[i] = *(const float*)(rec + (size_t)b * entry_bytes + (size_t)t * rec_stride +
-                                 rec_off + d * 4);
-    }
-}
-
-__global__ void ingest_scalar_kernel(const char* __restrict__ rec, int T, int B, int A,
-                                     int mu_off, int hdr_act, size_t rec_stride, size_t entry_bytes,
-                                     int32_t* act, float* rew, float* disc, int* bad) {
-    const size_t n = (size_t)T * B;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int t = (int)(i / B), b = (int)(i - (size_t)t * B);
-        const char* r = rec + (size_t)b * entry_bytes + (size_t)t * rec_stride + mu_off;
-        r += hdr_act;
-        int32_t a = *(const int32_t*)r;
-        if ((unsigned)a >= (unsigned)A && bad) atomicAdd(bad, 1);
-        act[i] = a < 0 ? 0 : (a >= A ? A - 1 : a);
-        rew[i] = *(const float*)(r + 4);
-        disc[i] = *(const float*)(r + 8);
-    }
-}
-
-// Frames of the Atari records -> the time-major frames tensor (T+1, B, 84, 84, 4): a strided
+// Frames of the stacked Atari records -> the time-major frames tensor (T+1, B, 84, 84, 4): a strided
 // de-interleave of whole 28,224-byte frames. A workgroup owns a frame and grid-strides over
 // frames, so the (t, b) index work is done once per frame on the scalar unit; its 256 lanes
 // move the frame's 1,764 16-byte pieces, 7 per lane, every load issued before the first store.
@@ -165,7 +111,7 @@ __global__ __launch_bounds__(256) void ingest_frames_kernel(const char* __restri
     for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
         const int t = f / B, b = f - t * B;
         const uint4* __restrict__ src =
-            (const uint4*)(rec + (size_t)b * entry_bytes + (size_t)t * FI_ATARI_RECORD_BYTES) + lane;
+            (const uint4*)(rec + (size_t)b * entry_bytes + (size_t)t * kAtariRecBytes) + lane;
         uint4* __restrict__ dst = frames + (size_t)f * kFramePieces + lane;
         uint4 v[kIngestFullRounds];
         uint4 vt = make_uint4(0u, 0u, 0u, 0u);
@@ -178,21 +124,23 @@ __global__ __launch_bounds__(256) void ingest_frames_kernel(const char* __restri
     }
 }
 
-int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_bytes, float* obs,
-                  float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad) {
-    FI_REQUIRE(rec && T >= 1 && B >= 1 && A >= 1 && A <= 64 && D <= 128, "ingest: bad shape");
-    FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * FI_RECORD_BYTES, "ingest: entry too small");
-    const char* r = (const char*)rec;
-    const size_t stride = FI_RECORD_BYTES;
-    if (obs)
-        hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)(T + 1) * B * D)), dim3(256), 0, s,
-                           r, T + 1, B, D, REC_OBS, stride, entry_bytes, obs);
-    if (mu)
-        hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T,
-                           B, A, REC_MU, stride, entry_bytes, mu);
-    if (act && rew && disc)
-        hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T,
-                           B, A, REC_MU, HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
+// mu and action / reward / discount of T records, rec_stride apart, with mu at mu_off and the action at act_off
+static void ingest_header(const Strided& at, int mu_off, int act_off, size_t rec_stride, const BatchTensors& to) {
+    launch_ingest_vec(at, to.T, to.B, to.A, mu_off, rec_stride, to.mu, to.stream);
+    launch_ingest_scalar<Strided, false>(at, to.T, to.B, to.A, act_off, rec_stride, to.act, to.rew, to.disc, to.bad,
+                                         nullptr, to.stream);
+}
+
+int ingest_launch(const void* rec, size_t entry_bytes, const BatchTensors& to) {
+    const int T = to.T, B = to.B;
+    FI_REQUIRE(rec && T >= 1 && B >= 1 && to.A >= 1 && to.A <= kMlpMaxActions && to.D <= kMlpMaxObs, "ingest: bad shape");
+    FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * kMlpRecBytes, "ingest: entry too small");
+    const Strided at{(const char*)rec, entry_bytes};
+    if (to.obs) launch_ingest_vec(at, T + 1, B, to.D, kMlpRecObs, kMlpRecBytes, to.obs, to.stream);
+    if (to.mu) launch_ingest_vec(at, T, B, to.A, kMlpRecMu, kMlpRecBytes, to.mu, to.stream);
+    if (to.act && to.rew && to.disc)
+        launch_ingest_scalar<Strided, false>(at, T, B, to.A, kMlpRecAct, kMlpRecBytes, to.act, to.rew, to.disc, to.bad,
+                                             nullptr, to.stream);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -200,125 +148,41 @@ int ingest_launch(const void* rec, int T, int B, int A, int D, size_t entry_byte
 // workgroups of the frame copy: 8 per CU on 256 CUs, the rest of the frames by grid stride
 constexpr int kIngestFramesMaxGrid = 2048;
 
-int ingest_atari_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
-                        float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad) {
-    FI_REQUIRE(rec && frames && mu && act && rew && disc, "ingest_atari: null argument");
-    FI_REQUIRE(T >= 1 && B >= 1 && A >= 1 && A <= 64, "ingest_atari: bad shape");
+int ingest_atari_launch(const void* rec, size_t entry_bytes, const BatchTensors& to) {
+    const int T = to.T, B = to.B, A = to.A;
+    FI_REQUIRE(rec && to.frames && to.mu && to.act && to.rew && to.disc, "ingest_atari: null argument");
+    FI_REQUIRE(T >= 1 && B >= 1 && A >= 1 && A <= kMlpMaxActions, "ingest_atari: bad shape");
     FI_REQUIRE((size_t)(T + 1) * (size_t)B <= (size_t)0x7fffffff, "ingest_atari: too many frames");
     FI_REQUIRE(entry_bytes % 16 == 0, "ingest_atari: entry_bytes must be a multiple of 16");
-    FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * FI_ATARI_RECORD_BYTES,
-               "ingest_atari: entry_bytes < " + std::to_string((size_t)(T + 1) * FI_ATARI_RECORD_BYTES) +
+    FI_REQUIRE(entry_bytes >= (size_t)(T + 1) * kAtariRecBytes,
+               "ingest_atari: entry_bytes < " + std::to_string((size_t)(T + 1) * kAtariRecBytes) +
                    " = (T+1)*28672");
-    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)frames % 16 == 0,
+    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)to.frames % 16 == 0,
                "ingest_atari: records and frames must be 16-byte aligned");
-    const char* r = (const char*)rec;
-    const size_t stride = FI_ATARI_RECORD_BYTES;
     const int n_frames = (T + 1) * B;
-    hipLaunchKernelGGL(ingest_frames_kernel, dim3(std::min(n_frames, kIngestFramesMaxGrid)), dim3(256), 0, s,
-                       r, n_frames, B, entry_bytes, (uint4*)frames);
-    hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T, B, A,
-                       ATARI_REC_MU, stride, entry_bytes, mu);
-    hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T, B, A,
-                       ATARI_REC_MU, HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
+    hipLaunchKernelGGL(ingest_frames_kernel, dim3(std::min(n_frames, kIngestFramesMaxGrid)), dim3(256), 0, to.stream,
+                       (const char*)rec, n_frames, B, entry_bytes, (uint4*)to.frames);
+    ingest_header(Strided{(const char*)rec, entry_bytes}, kAtariRecMu, kAtariRecAct, kAtariRecBytes, to);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
 
-// Plane records -> the same frames tensor: channel c of frame t is the plane of step t-3+c, the
-// first observation of an episode filling all four channels (the frame-stack wrapper's rule,
-// DESIGN.md section 3). A byte interleave of four planes into 4-byte pixels that reads every
-// plane from HBM once.
-//   A one-wave workgroup owns an entry b and a run of 64 16-byte plane pieces (1,024 pixels) and
-// walks t forward: -3..-1 take the history block's planes, 0..T the records'. Each step a lane
-// loads its 16-byte piece (the next step's is requested before this step's stores), the wave
-// turns the 256 dwords through LDS so that lane j holds dwords 64k + j (k = 0..3), and the lane
-// keeps the three previous steps' four dwords in registers. Output piece 64k + j of the run is
-// then the byte interleave of dword 64k + j of the four channels (two levels of v_perm_b32), so
-// each of the four 16-byte stores of a step is contiguous over the wave (1 KiB). episode_start
-// is uniform per (t, b): one scalar load and a uniform branch. 7 runs cover the 441 pieces (the
-// last has 57); 7 B workgroups, no grid cap.
-constexpr int PLANE_REC = FI_ATARI_PLANE_RECORD_BYTES;
-constexpr int kPlaneBytes = 84 * 84;
-constexpr int kPlanePieces = kPlaneBytes / 16;                // 441 16-byte pieces per plane
-constexpr int kPlaneRuns = (kPlanePieces + 63) / 64;          // 7 runs of 64 pieces
-constexpr int PLANE_REC_MU = kPlaneBytes, PLANE_HDR_ACT = 72;  // action at 7128, +4 reward, +8 discount
-constexpr int PLANE_REC_START = 7144;
-constexpr int kPlaneMaxActions = 18;
-static_assert(kPlanePieces * 16 == kPlaneBytes, "a plane is a whole number of 16-byte pieces");
-static_assert(PLANE_REC_MU + 4 * kPlaneMaxActions == PLANE_REC_MU + PLANE_HDR_ACT, "compact header: mu[18], action");
-static_assert(PLANE_REC_START + 4 <= PLANE_REC, "plane record header");
-static_assert(PLANE_REC == FI_ATARI_PLANE_RECORD_ELEMENTS * FI_RECORD_BYTES, "plane record size");
-static_assert(3 * kPlaneBytes <= FI_ATARI_HISTORY_BYTES &&
-                  FI_ATARI_HISTORY_BYTES == FI_ATARI_HISTORY_ELEMENTS * FI_RECORD_BYTES, "history block");
-
-// interleave4 (4 pixels of channels 0..3 -> 4 NHWC pixels): interleave.h, shared with gather.hip
-
-__global__ __launch_bounds__(64) void ingest_planes_kernel(const char* __restrict__ rec, int T, int B,
-                                                           size_t entry_bytes, uint4* __restrict__ frames) {
-    __shared__ uint4 turn[2][64];  // two buffers: one barrier per step
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x / kPlaneRuns, run = blockIdx.x - b * kPlaneRuns;
-    const int piece = run * 64 + lane;
-    const bool live = piece < kPlanePieces;  // the loads of the last run's 7 spare lanes are skipped
-    const char* __restrict__ entry = rec + (size_t)b * entry_bytes;
-    const uint4* __restrict__ hist = (const uint4*)(entry + (size_t)(T + 1) * PLANE_REC);
-    uint32_t w0[4] = {}, w1[4] = {}, w2[4] = {};  // this lane's dwords of the three previous steps
-    uint4 next = make_uint4(0u, 0u, 0u, 0u);
-    if (live) next = hist[piece];
-    for (int t = -3; t <= T; ++t) {
-        const uint4 cur = next;
-        if (t < T && live) {
-            const uint4* src = t + 1 < 0 ? hist + (t + 4) * kPlanePieces
-                                         : (const uint4*)(entry + (size_t)(t + 1) * PLANE_REC);
-            next = src[piece];
-        }
-        uint4* x = turn[t & 1];
-        x[lane] = cur;
-        __syncthreads();
-        const uint32_t* xd = (const uint32_t*)x;
-        uint32_t n[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) n[k] = xd[64 * k + lane];
-        if (t >= 0) {
-            if (*(const uint32_t*)(entry + (size_t)t * PLANE_REC + PLANE_REC_START) != 0u) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w0[k] = w1[k] = w2[k] = n[k];
-            }
-            uint4* __restrict__ dst = frames + ((size_t)t * B + b) * kFramePieces + run * 256 + lane;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (run * 256 + 64 * k + lane < kFramePieces) dst[64 * k] = interleave4(w0[k], w1[k], w2[k], n[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            w0[k] = w1[k];
-            w1[k] = w2[k];
-            w2[k] = n[k];
-        }
-    }
-}
-
-int ingest_atari_planes_launch(const void* rec, int T, int B, int A, size_t entry_bytes, uint8_t* frames,
-                               float* mu, int32_t* act, float* rew, float* disc, hipStream_t s, int* bad) {
-    FI_REQUIRE(rec && frames && mu && act && rew && disc, "ingest_atari_planes: null argument");
+int ingest_atari_planes_launch(const void* rec, size_t entry_bytes, const BatchTensors& to) {
+    const int T = to.T, B = to.B, A = to.A;
+    FI_REQUIRE(rec && to.frames && to.mu && to.act && to.rew && to.disc, "ingest_atari_planes: null argument");
     FI_REQUIRE(T >= 1 && B >= 1 && A >= 1, "ingest_atari_planes: bad shape");
     FI_REQUIRE(A <= kPlaneMaxActions, "ingest_atari_planes: the plane record's header holds mu[18]: A = " +
                                           std::to_string(A) + " > 18");
     FI_REQUIRE((size_t)(T + 1) * (size_t)B <= (size_t)0x7fffffff / kPlaneRuns, "ingest_atari_planes: too many frames");
     FI_REQUIRE(entry_bytes % 16 == 0, "ingest_atari_planes: entry_bytes must be a multiple of 16");
-    const size_t need = (size_t)(T + 1) * PLANE_REC + FI_ATARI_HISTORY_BYTES;
+    const size_t need = plane_history_offset(T) + kHistoryBytes;
     FI_REQUIRE(entry_bytes >= need, "ingest_atari_planes: entry_bytes < " + std::to_string(need) +
                                         " = (T+1)*7168 + 21504");
-    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)frames % 16 == 0,
+    FI_REQUIRE((uintptr_t)rec % 16 == 0 && (uintptr_t)to.frames % 16 == 0,
                "ingest_atari_planes: records and frames must be 16-byte aligned");
-    const char* r = (const char*)rec;
-    const size_t stride = PLANE_REC;
-    hipLaunchKernelGGL(ingest_planes_kernel, dim3((unsigned)(B * kPlaneRuns)), dim3(64), 0, s, r, T, B, entry_bytes,
-                       (uint4*)frames);
-    hipLaunchKernelGGL(ingest_vec_kernel, dim3(grid_for((size_t)T * B * A)), dim3(256), 0, s, r, T, B, A,
-                       PLANE_REC_MU, stride, entry_bytes, mu);
-    hipLaunchKernelGGL(ingest_scalar_kernel, dim3(grid_for((size_t)T * B)), dim3(256), 0, s, r, T, B, A,
-                       PLANE_REC_MU, PLANE_HDR_ACT, stride, entry_bytes, act, rew, disc, bad);
+    const Strided at{(const char*)rec, entry_bytes};
+    launch_ingest_planes(at, T, B, to.frames, to.stream);
+    ingest_header(at, kPlaneRecMu, kPlaneRecAct, kPlaneRecBytes, to);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -591,23 +455,28 @@ extern "C" int fi_synth_trajectories(uint64_t seed, int T, int B, int B_glob, in
                             (hipStream_t)stream);
 }
 
+// the standalone entry points: the tensors the caller names, no reject counter
+static fi::BatchTensors tensors_of(int arch, int T, int B, int A, int D, float* obs, uint8_t* frames, float* mu,
+                                   int32_t* act, float* rew, float* disc, void* stream) {
+    return fi::BatchTensors{arch, T, B, A, D, obs, frames, mu, act, rew, disc, nullptr, nullptr, nullptr, (hipStream_t)stream};
+}
+
 extern "C" int fi_ingest_records(const void* rec, int T, int B, int A, int D, size_t entry_bytes,
                                  float* obs, float* mu, int32_t* act, float* rew, float* disc,
                                  void* stream) {
-    return fi::ingest_launch(rec, T, B, A, D, entry_bytes, obs, mu, act, rew, disc,
-                             (hipStream_t)stream);
+    return fi::ingest_launch(rec, entry_bytes, tensors_of(FI_ARCH_MLP, T, B, A, D, obs, nullptr, mu, act, rew, disc, stream));
 }
 
 extern "C" int fi_ingest_atari_records(const void* rec, int T, int B, int A, size_t entry_bytes,
                                        uint8_t* frames, float* mu, int32_t* act, float* rew,
                                        float* disc, void* stream) {
-    return fi::ingest_atari_launch(rec, T, B, A, entry_bytes, frames, mu, act, rew, disc,
-                                   (hipStream_t)stream);
+    return fi::ingest_atari_launch(rec, entry_bytes,
+                                   tensors_of(FI_ARCH_ATARI, T, B, A, 0, nullptr, frames, mu, act, rew, disc, stream));
 }
 
 extern "C" int fi_ingest_atari_planes(const void* rec, int T, int B, int A, size_t entry_bytes,
                                       uint8_t* frames, float* mu, int32_t* act, float* rew,
                                       float* disc, void* stream) {
-    return fi::ingest_atari_planes_launch(rec, T, B, A, entry_bytes, frames, mu, act, rew, disc,
-                                          (hipStream_t)stream);
+    return fi::ingest_atari_planes_launch(rec, entry_bytes,
+                                          tensors_of(FI_ARCH_ATARI, T, B, A, 0, nullptr, frames, mu, act, rew, disc, stream));
 }

@@ -14,6 +14,7 @@
 
 #include "fi_common.h"
 #include "fi_ring.h"
+#include "ingest_kernels.h"
 #include "kernels.h"
 
 namespace fi {
@@ -21,12 +22,7 @@ namespace fi {
 namespace {
 constexpr int kChunkPieces = 1024;  // 16-byte pieces a workgroup copies: 256 lanes x 4, 16 KiB
 constexpr int64_t kMaxCapacity = 0x7fffffff;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld16(const char* p) {
-    const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
+// ld16 (a 16-byte load that names the global address space): ingest_kernels.h
 }  // namespace
 
 // ---------------------------------------------------------------- the push's copy
@@ -129,13 +125,9 @@ int ring_columns_launch(const RingBatch& rb, const void** cols, int B, uint32_t*
 }
 
 // what a learner's step from a ring enqueues as its ingest (learner.cpp: learner_step_columns)
-static int learner_ring_ingest(const void* ctx, const GatherTargets& to) {
+static int learner_ring_ingest(const void* ctx, const BatchTensors& to) {
     FI_TRY(ring_columns_launch(*(const RingBatch*)ctx, to.cols, to.B, to.versions, to.stream));
-    if (to.arch == FI_ARCH_MLP)
-        return gather_records_launch(to.cols, to.T, to.B, to.A, to.D, to.obs, to.mu, to.act, to.rew, to.disc, to.stream,
-                                     to.bad, to.versions);
-    return gather_atari_planes_launch(to.cols, to.T, to.B, to.A, to.frames, to.mu, to.act, to.rew, to.disc, to.stream,
-                                      to.bad, to.versions);
+    return gather_ingest(to);
 }
 
 }  // namespace fi

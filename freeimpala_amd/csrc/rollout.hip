@@ -10,21 +10,18 @@
 #include "fi_common.h"
 #include "fi_rollout.h"
 #include "kernels.h"
+#include "records.h"
 
 namespace fi {
 
 namespace {
-constexpr int kPlaneBytes = 84 * 84;
-constexpr int kPlanePieces = kPlaneBytes / 16;        // 441
-constexpr int kPlaneRuns = (kPlanePieces + 63) / 64;  // 7
-constexpr int kStackPieces = 4 * kPlanePieces;        // 1,764
-constexpr int kRec = FI_ATARI_PLANE_RECORD_BYTES;
-// dword offsets of the header fields behind the plane
-// (the reward and the discount, dwords 19 and 20, are the outcome scatter's: kPlaneRecReward)
-constexpr int kHdrMu = 0, kHdrAct = 18, kHdrFlags = 21, kHdrStart = 22;
-static_assert(kPlaneRecReward == (size_t)kPlaneBytes + 4 * 19 && kMlpRecReward == 4 * 193, "reward, then discount");
-constexpr int kPlaneMaxActions = 18;
-static_assert(kPlaneBytes + 4 * (kHdrStart + 1) <= kRec && kPlaneBytes % 16 == 0 && kRec % 16 == 0, "record layout");
+constexpr int kStackPieces = kFramePieces;  // an actor's stack is one frame: 1,764 16-byte pieces
+constexpr int kRec = kPlaneRecBytes;
+// dword indices of the plane record's header fields, from its mu (records.h; the reward and the
+// discount between the action and the flags are the outcome scatter's)
+constexpr int kDwMu = 0, kDwAct = (kPlaneRecAct - kPlaneRecMu) / 4, kDwFlags = (kPlaneRecFlags - kPlaneRecMu) / 4,
+              kDwStart = (kPlaneRecStart - kPlaneRecMu) / 4;
+static_assert(kDwAct == kPlaneMaxActions && kDwStart < 64, "the header's dwords: one per lane of the last run's wave");
 }  // namespace
 
 // ---------------------------------------------------------------- one step's plane record
@@ -51,11 +48,11 @@ __global__ __launch_bounds__(64) void record_planes_kernel(char* __restrict__ re
     const uint32_t fsh = (uint32_t)((uintptr_t)fp & 3u);
     const uint32_t fword = *(const uint32_t*)(fp - fsh);
     const uint32_t first = ((fword >> (8u * fsh)) & 0xffu) != 0u ? 1u : 0u;
-    if (lane == kHdrStart) hdr[kHdrStart] = first;
+    if (lane == kDwStart) hdr[kDwStart] = first;
     if (!logits) return;
-    if (lane < A) hdr[kHdrMu + lane] = __float_as_uint(logits[(size_t)env * A + lane]);
-    if (lane == kHdrAct) hdr[kHdrAct] = (uint32_t)actions[env];
-    if (lane == kHdrFlags) hdr[kHdrFlags] = flags;
+    if (lane < A) hdr[kDwMu + lane] = __float_as_uint(logits[(size_t)env * A + lane]);
+    if (lane == kDwAct) hdr[kDwAct] = (uint32_t)actions[env];
+    if (lane == kDwFlags) hdr[kDwFlags] = flags;
 }
 
 int record_planes_launch(void* entries, size_t stride, int t, const uint8_t* planes, const uint8_t* start,
@@ -124,9 +121,9 @@ int extract_history_launch(void* entries, size_t stride, size_t hist_off, const 
     FI_REQUIRE(N >= 1 && N <= 0x7fffffff / kPlaneRuns, "extract_history: N must be >= 1");
     FI_REQUIRE((uintptr_t)entries % 16 == 0 && stride % 16 == 0 && hist_off % 16 == 0 && (uintptr_t)stacks % 16 == 0,
                "extract_history: entries, entry_stride, history_offset and stacks must be 16-byte aligned");
-    FI_REQUIRE(stride >= hist_off + 3 * (size_t)kPlaneBytes,
+    FI_REQUIRE(stride >= hist_off + kHistoryPlanes * (size_t)kPlaneBytes,
                "extract_history: entry_stride " + std::to_string(stride) + " < history_offset + 21168 = " +
-                   std::to_string(hist_off + 3 * (size_t)kPlaneBytes));
+                   std::to_string(hist_off + kHistoryPlanes * (size_t)kPlaneBytes));
     hipLaunchKernelGGL(extract_history_kernel, dim3((unsigned)(N * kPlaneRuns)), dim3(64), 0, s,
                        (char*)entries + hist_off, stride, (const uint4*)stacks);
     FI_HIP_CHECK(hipGetLastError());
@@ -136,7 +133,7 @@ int extract_history_launch(void* entries, size_t stride, size_t hist_off, const 
 // ---------------------------------------------------------------- one step's MLP record
 // rec = entries + t * 1024. One wave per environment, one dword per lane and store: the D <= 128
 // observation floats at byte 0, with logits also mu[lane] at 512, the action at 768 and the flags
-// word at 780 (record schema: DESIGN.md section 3). The observation rows are D floats apart, so
+// word at 780 (record schema: records.h). The observation rows are D floats apart, so
 // for a D that is no multiple of 4 they are not 16-byte aligned: dword accesses, contiguous over
 // the wave.
 __global__ __launch_bounds__(64) void record_obs_kernel(char* __restrict__ rec, size_t stride,
@@ -149,19 +146,19 @@ __global__ __launch_bounds__(64) void record_obs_kernel(char* __restrict__ rec, 
     const uint32_t* __restrict__ o = (const uint32_t*)(obs + (size_t)env * D);
     for (int i = lane; i < D; i += 64) r[i] = o[i];
     if (!logits) return;
-    if (lane < A) r[128 + lane] = __float_as_uint(logits[(size_t)env * A + lane]);
-    if (lane == 0) r[192] = (uint32_t)actions[env];
-    if (lane == 1) r[195] = flags;
+    if (lane < A) r[kMlpRecMu / 4 + lane] = __float_as_uint(logits[(size_t)env * A + lane]);
+    if (lane == 0) r[kMlpRecAct / 4] = (uint32_t)actions[env];
+    if (lane == 1) r[kMlpRecFlags / 4] = flags;
 }
 
 int record_obs_launch(void* entries, size_t stride, int t, const float* obs, int D, const float* logits,
                       const int32_t* actions, uint32_t flags, int N, int A, hipStream_t s) {
     FI_REQUIRE(entries && obs, "record_obs: null argument");
     FI_REQUIRE(!logits || actions, "record_obs: logits without actions");
-    FI_REQUIRE(N >= 1 && D >= 1 && D <= 128 && A >= 2 && A <= 64 && t >= 0, "record_obs: bad shape");
+    FI_REQUIRE(N >= 1 && D >= 1 && D <= kMlpMaxObs && A >= 2 && A <= kMlpMaxActions && t >= 0, "record_obs: bad shape");
     FI_REQUIRE((uintptr_t)entries % 4 == 0 && stride % 4 == 0, "record_obs: entries and entry_stride must be 4-byte aligned");
-    FI_REQUIRE(stride >= ((size_t)t + 1) * FI_RECORD_BYTES, "record_obs: entry_stride < (t+1)*1024");
-    hipLaunchKernelGGL(record_obs_kernel, dim3((unsigned)N), dim3(64), 0, s, (char*)entries + (size_t)t * FI_RECORD_BYTES,
+    FI_REQUIRE(stride >= ((size_t)t + 1) * kMlpRecBytes, "record_obs: entry_stride < (t+1)*1024");
+    hipLaunchKernelGGL(record_obs_kernel, dim3((unsigned)N), dim3(64), 0, s, (char*)entries + (size_t)t * kMlpRecBytes,
                        stride, obs, D, logits, actions, flags, A);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;

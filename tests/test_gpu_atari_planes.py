@@ -11,7 +11,7 @@ from test_atari_plane_records import rand_planes
 pytestmark = pytest.mark.gpu
 
 REC, PLANE, HIST, FRAME = 7168, 84 * 84, 21504, 84 * 84 * 4
-# ingest_planes_kernel (csrc/misc.hip) launches 7 one-wave workgroups per entry (runs of 64 of a
+# ingest_planes_kernel (csrc/ingest_kernels.h) launches 7 one-wave workgroups per entry (runs of 64 of a
 # plane's 441 16-byte pieces) with no grid cap and walks all of T in one pass: no grid-stride
 # wrap and no segment boundary to cover. (1, 300) puts 2,100 workgroups on the device.
 PLANE_RUNS = 7
