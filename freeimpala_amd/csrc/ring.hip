@@ -16,6 +16,7 @@
 #include "fi_ring.h"
 #include "ingest_kernels.h"
 #include "kernels.h"
+#include "ring_handle.h"
 
 namespace fi {
 
@@ -75,16 +76,7 @@ int ring_push_launch(void* ring, size_t entry_bytes, int64_t capacity, uint64_t 
 }
 
 // ---------------------------------------------------------------- the batch rule
-// the numbers of one batch, taken before the call (include/fi_ring.h)
-struct RingBatch {
-    const char* base;
-    size_t entry_bytes;
-    uint32_t C;
-    int32_t n_fresh;
-    uint64_t tail, lo, n_valid, seed, draw;
-    uint64_t* entries_out;  // nullable
-};
-
+// the numbers of one batch, taken before the call (include/fi_ring.h): RingBatch, ring_handle.h
 // Column c < n_fresh: entry tail + c. Column c >= n_fresh: entry lo + ((x * n_valid) >> 32), x the
 // first word of philox4(seed, draw * B + c, ST_REPLAY); n_valid <= C < 2^31, so the product stays
 // inside 64 bits. Thread 0 also puts the version block into its neutral state, as
@@ -134,25 +126,16 @@ static int learner_ring_ingest(const void* ctx, const BatchTensors& to) {
 
 using namespace fi;
 
-// ------------------------------------------------------------------ the handle
-struct fi_ring {
-    int dev = 0;
-    size_t entry = 0;
-    int64_t C = 0;
-    uint64_t seed = 0, draw = 0;
-    uint64_t head = 0, tail = 0;
-    char* base = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t pushed = nullptr;
-    bool have_pushed = false;
-    uint64_t* last = nullptr;  // the entries of the last ring step, 8 * last_cap bytes
-    int last_cap = 0, last_n = 0;
-};
-
+// ------------------------------------------------------------------ the handle (struct fi_ring: ring_handle.h)
 static void destroy(fi_ring* r) {
     if (!r) return;
     (void)hipSetDevice(r->dev);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
+    if (r->have_prio_done) (void)hipEventSynchronize(r->prio_done);  // behind the last refresh (fi_prio.h)
+    if (r->prio_q) (void)hipFree(r->prio_q);
+    if (r->prio_sums) (void)hipFree(r->prio_sums);
+    if (r->prio) (void)hipFree(r->prio);
+    if (r->prio_done) (void)hipEventDestroy(r->prio_done);
     if (r->last) (void)hipFree(r->last);
     if (r->base) (void)hipFree(r->base);
     if (r->pushed) (void)hipEventDestroy(r->pushed);
@@ -320,8 +303,8 @@ extern "C" int fi_ring_last_entries(fi_ring* r, uint64_t* dst, int32_t n) {
 // ------------------------------------------------------------------ the learner steps from a ring
 // It lives here, not in learner.cpp, because it holds both handles (as fi_learner_step_rollout in
 // actor.hip): every refusal is made here, before learner.cpp enqueues anything.
-static int step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out, bool wait, const char* who) {
-    const std::string nm = who;
+int fi::ring_step_check(fi_learner* l, fi_ring* r, int32_t n_fresh, const std::string& nm, LearnerInfo* li_out,
+                        RingBatch* rb) {
     FI_REQUIRE(l && r, nm + ": null argument");
     LearnerInfo li{};
     FI_TRY(learner_info(l, &li));
@@ -344,36 +327,55 @@ static int step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
         return fail(FI_ERR_STATE, nm + ": nothing to replay: " + std::to_string(li.B - n_fresh) +
                                       " columns of the batch " + std::to_string(li.B) +
                                       " are replayed and no entry was read yet (tail " + std::to_string(r->tail) + ")");
+    *li_out = li;
+    *rb = RingBatch{r->base, r->entry, (uint32_t)r->C, n_fresh, r->tail, lo, n_valid, r->seed, r->draw, nullptr};
+    return FI_OK;
+}
+
+int fi::ring_step_entries(fi_ring* r, int B, const std::string& nm) {
     FI_HIP_CHECK(hipSetDevice(r->dev));
-    if (r->last_cap < li.B) {
+    if (r->last_cap < B) {
         if (r->last) {
             FI_HIP_CHECK(hipStreamSynchronize(r->stream));  // behind the last step's columns kernel
             (void)hipFree(r->last);
             r->last = nullptr;
             r->last_cap = r->last_n = 0;
         }
-        const hipError_t e = hipMalloc((void**)&r->last, 8 * (size_t)li.B);
+        const hipError_t e = hipMalloc((void**)&r->last, 8 * (size_t)B);
         if (e != hipSuccess) {
             r->last = nullptr;
             (void)hipGetLastError();
-            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(8 * (size_t)li.B) + ") for the entry indices");
+            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(8 * (size_t)B) + ") for the entry indices");
         }
-        r->last_cap = li.B;
+        r->last_cap = B;
     }
-    const RingBatch rb{r->base, r->entry, (uint32_t)r->C, n_fresh, r->tail, lo, n_valid, r->seed, r->draw, r->last};
-    const int rc = learner_step_columns(l, r->have_pushed ? r->pushed : nullptr, learner_ring_ingest, &rb, out, wait, who);
-    // as fi_learner_step_rollouts: the batch counts as taken when the step ran (FI_ERR_NONFINITE: it
-    // ran and skipped its update) or, asynchronously, was enqueued; after any other status the
-    // counters stay
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
+    return FI_OK;
+}
+
+int fi::ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B, int rc) {
     std::string why;
     if (rc != FI_OK) why = fi_last_error();
     // a later push may overwrite the slots this batch names: it goes behind the ingest
     FI_HIP_CHECK(hipStreamWaitEvent(r->stream, (hipEvent_t)fi_learner_entries_consumed_event(l), 0));
     r->tail += (uint64_t)n_fresh;
     r->draw += 1;
-    r->last_n = li.B;
+    r->last_n = B;
     return rc == FI_OK ? FI_OK : fail(rc, why);
+}
+
+static int step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out, bool wait, const char* who) {
+    const std::string nm = who;
+    LearnerInfo li{};
+    RingBatch rb{};
+    FI_TRY(ring_step_check(l, r, n_fresh, nm, &li, &rb));
+    FI_TRY(ring_step_entries(r, li.B, nm));
+    rb.entries_out = r->last;
+    const int rc = learner_step_columns(l, r->have_pushed ? r->pushed : nullptr, learner_ring_ingest, &rb, out, wait, who);
+    // as fi_learner_step_rollouts: the batch counts as taken when the step ran (FI_ERR_NONFINITE: it
+    // ran and skipped its update) or, asynchronously, was enqueued; after any other status the
+    // counters stay
+    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
+    return ring_step_taken(l, r, n_fresh, li.B, rc);
 }
 
 extern "C" int fi_learner_step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out) {

@@ -185,12 +185,24 @@ class DeviceLearner:
               "fi_learner_step_rollouts_async")
 
     # --- a batch chosen from a device entry ring (include/fi_ring.h)
-    def step_ring(self, ring, n_fresh: int | None = None, wait: bool = True) -> dict | None:
+    def step_ring(self, ring, n_fresh: int | None = None, wait: bool = True, prioritized: bool = False) -> dict | None:
         """Step from an ``EntryRing``: the first n_fresh columns (default: all B, the reference's
         readBatch(B)) take the oldest unread entries, the others are replayed from the entries read
-        before that are still resident. wait=False: enqueued only, see wait()."""
+        before that are still resident. wait=False: enqueued only, see wait(). prioritized=True
+        (after ``ring.enable_priorities()``): the replayed columns are drawn in proportion to the
+        entries' priorities, which the step refreshes (include/fi_prio.h)."""
         from . import ring as ring_mod
         n = self.B if n_fresh is None else n_fresh
+        if prioritized:
+            from . import prio
+            if not wait:
+                check(prio.lib().fi_learner_step_ring_prioritized_async(self._h, ring._h, n),
+                      "fi_learner_step_ring_prioritized_async")
+                return None
+            st = _abi.StepStats()
+            check(prio.lib().fi_learner_step_ring_prioritized(self._h, ring._h, n, C.byref(st)),
+                  "fi_learner_step_ring_prioritized")
+            return st.as_dict()
         if not wait:
             check(ring_mod.lib().fi_learner_step_ring_async(self._h, ring._h, n), "fi_learner_step_ring_async")
             return None

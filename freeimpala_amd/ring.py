@@ -140,6 +140,32 @@ class EntryRing:
         check(lib().fi_ring_last_entries(self._h, out.ctypes.data, B), "fi_ring_last_entries")
         return [int(e) for e in out[:B]]
 
+    # --- prioritised replay (include/fi_prio.h; prio.py)
+    def enable_priorities(self, eta: float = 0.9, init_priority: float = 1.0) -> None:
+        """A u32 priority per slot: ``DeviceLearner.step_ring(prioritized=True)`` draws its replayed
+        columns in proportion to it and refreshes it from the step's TD magnitudes."""
+        from . import prio
+        prio.enable(self, eta, init_priority)
+
+    def priority_info(self) -> dict:
+        """dict(enabled, eta, q_init, prio_hi, table_bytes)."""
+        from . import prio
+        return prio.info(self)
+
+    def priorities(self, first_entry: int | None = None, n: int | None = None) -> np.ndarray:
+        """(n,) uint32: the priorities of the entries first_entry .. first_entry + n - 1 (by default
+        the whole replayable window [lo, tail))."""
+        from . import prio
+        i = self.info()
+        lo = max(0, i["head"] - i["capacity"])
+        first = lo if first_entry is None else first_entry
+        return prio.read(self, first, i["tail"] - first if n is None else n)
+
+    def set_priorities(self, first_entry: int, q) -> None:
+        """The priorities of the entries first_entry .. first_entry + len(q) - 1, inside [lo, tail)."""
+        from . import prio
+        prio.write(self, first_entry, q)
+
     def close(self) -> None:
         if self._h:
             lib().fi_ring_destroy(self._h)
