@@ -217,6 +217,60 @@ class Actor:
         from . import rollout
         check(rollout.lib().fi_rollout_end(self._h), "fi_rollout_end")
 
+    # --- device pointers in, nothing waits (include/fi_env.h). Pointers and events travel as ints.
+    def act_planes_dev(self, planes_ptr: int, episode_start_ptr: int, ready_event=None) -> None:
+        """Enqueue an act call on N*7056 plane bytes and N start flags in device memory."""
+        from . import env
+        check(env.lib().fi_actor_act_planes_dev(self._h, planes_ptr, episode_start_ptr, ready_event),
+              "fi_actor_act_planes_dev")
+
+    def act_obs_dev(self, obs_ptr: int, ready_event=None) -> None:
+        """Enqueue an act call on N*obs_dim floats in device memory (MLP)."""
+        from . import env
+        check(env.lib().fi_actor_act_obs_dev(self._h, obs_ptr, ready_event), "fi_actor_act_obs_dev")
+
+    def outputs_dev(self) -> dict:
+        """Device pointers of the handle's actions int32[N], logits float[N*A], values float[N] and
+        the event behind the last device call (None before the first)."""
+        from . import env
+        p = [_P() for _ in range(4)]
+        check(env.lib().fi_actor_outputs_dev(self._h, *[C.byref(x) for x in p]), "fi_actor_outputs_dev")
+        return dict(zip(("actions", "logits", "values", "done_event"), [x.value for x in p]))
+
+    def read_outputs(self) -> dict:
+        """Waits for the stream and copies the last act call's outputs to the host."""
+        from . import hip
+        self.sync()
+        o = self.outputs_dev()
+        return dict(actions=hip.download_ptr(o["actions"], np.int32, (self.N,)),
+                    logits=hip.download_ptr(o["logits"], np.float32, (self.N, self.A)),
+                    values=hip.download_ptr(o["values"], np.float32, (self.N,)))
+
+    def outcome_dev(self, rewards_ptr: int, discounts_ptr: int, ready_event=None) -> None:
+        """``outcome`` from N rewards and N discounts in device memory."""
+        from . import env
+        check(env.lib().fi_rollout_outcome_dev(self._h, rewards_ptr, discounts_ptr, ready_event),
+              "fi_rollout_outcome_dev")
+
+    @property
+    def stream(self) -> int | None:
+        """The handle's hipStream_t (where the device calls are enqueued)."""
+        from . import env
+        return env.lib().fi_actor_stream(self._h)
+
+    def sync(self) -> int:
+        """Wait for the handle's stream. Rows with NaN / Inf logits in the device act calls since the
+        last sync raise FiError (rc = FI_ERR_NONFINITE) with the count in ``nonfinite_rows``."""
+        from . import env
+        n = C.c_int64(0)
+        rc = env.lib().fi_actor_sync(self._h, C.byref(n))
+        try:
+            check(rc, "fi_actor_sync")
+        except _abi.FiError as e:
+            e.nonfinite_rows = n.value
+            raise
+        return n.value
+
     # --- profiling
     def set_profiling(self, on: bool) -> None:
         check(lib().fi_actor_set_profiling(self._h, int(on)), "fi_actor_set_profiling")

@@ -10,6 +10,8 @@
 //     host reference reproduces (fi_actor.h)
 //   * a recording handle (fi_rollout.h) also writes every step into the learner's entry format in
 //     device memory, with the kernels of rollout.hip, and hands completed unrolls to a learner
+//   * the act call and the outcome on device pointers (fi_env.h) enqueue the same launches on the
+//     caller's memory, without the copies and without the wait
 // One HIP stream per handle, no global mutable state, no HIP graphs.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +25,7 @@
 #include "atari.h"
 #include "fi_actor.h"
 #include "fi_common.h"
+#include "fi_env.h"
 #include "fi_rollout.h"
 #include "kernels.h"
 #include "records.h"
@@ -227,6 +230,12 @@ struct fi_actor {
     double phase_sum[PH_COUNT] = {};
     int phase_calls = 0;
     std::vector<void*> allocs;
+    // device act calls (fi_env.h), made by the first one: the event behind the last of them, the
+    // count of non-finite rows they add to until fi_actor_sync reads it, and whether one was
+    // enqueued since the host last waited for the stream
+    hipEvent_t dev_done = nullptr;
+    int* dev_bad = nullptr;
+    bool dev_pending = false;
     // rollout recording (fi_rollout.h): two device buffers of N entries; buf[fill] takes the unroll
     // being acted, buf[ready] (or -1) holds a completed unroll until it is released
     struct {
@@ -274,6 +283,7 @@ static void destroy(fi_actor* a) {
     if (a->pin_out) (void)hipHostFree(a->pin_out);
     for (auto& e : a->ev)
         if (e) (void)hipEventDestroy(e);
+    if (a->dev_done) (void)hipEventDestroy(a->dev_done);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -439,7 +449,7 @@ extern "C" int fi_actor_seed(fi_actor* a, uint64_t seed, uint64_t draw) {
 }
 
 // ------------------------------------------------------------------ the act call
-static int mlp_forward(fi_actor* a, float* logits, float* values) {
+static int mlp_forward(fi_actor* a, const float* obs, float* logits, float* values) {
     const int D = a->D, H = a->H, A = a->A;
     const float* W1 = a->params;
     const float* b1 = W1 + (size_t)D * H;
@@ -447,7 +457,7 @@ static int mlp_forward(fi_actor* a, float* logits, float* values) {
     const float* b2 = W2 + (size_t)H * H;
     const float* Wh = b2 + H;
     const float* bh = Wh + (size_t)H * (A + 1);
-    FI_TRY(f32_linear_fwd(a->obs, a->N, D, W1, b1, H, true, a->h1, a->stream));
+    FI_TRY(f32_linear_fwd(obs, a->N, D, W1, b1, H, true, a->h1, a->stream));
     FI_TRY(f32_linear_fwd(a->h1, a->N, H, W2, b2, H, true, a->h2, a->stream));
     FI_TRY(f32_heads_fwd(a->h2, a->N, H, Wh, bh, A, logits, values, a->stream));
     return FI_OK;
@@ -455,16 +465,18 @@ static int mlp_forward(fi_actor* a, float* logits, float* values) {
 
 // One act call's records (fi_rollout.h, the recording rule), enqueued on the handle's stream. The
 // call's device tensors -- planes and flags (obs), logits, actions, the stacks -- stay as they are
-// until the next act call's H2D copy, which follows in stream order.
-static int record_step(fi_actor* a, int kind, bool completing, const float* d_log, const int32_t* d_act) {
+// until the next act call's H2D copy, which follows in stream order. d_in / d_start: the planes
+// and flags (the observations) the call ran on -- the handle's own after a host call, the caller's
+// in a device call (fi_env.h).
+static int record_step(fi_actor* a, int kind, bool completing, const void* d_in, const uint8_t* d_start,
+                       const float* d_log, const int32_t* d_act) {
     auto& ro = a->ro;
     const uint32_t flags = (uint32_t)a->version;
-    const uint8_t* d_start = a->planes ? a->planes + (size_t)a->N * kPlaneBytes : nullptr;
     auto put = [&](int b, int t, bool whole) -> int {
         if (kind == IN_PLANES)
-            return record_planes_launch(ro.buf[b], ro.entry, t, a->planes, d_start, whole ? d_log : nullptr,
+            return record_planes_launch(ro.buf[b], ro.entry, t, (const uint8_t*)d_in, d_start, whole ? d_log : nullptr,
                                         whole ? d_act : nullptr, flags, a->N, a->A, a->stream);
-        return record_obs_launch(ro.buf[b], ro.entry, t, a->obs, a->D, whole ? d_log : nullptr,
+        return record_obs_launch(ro.buf[b], ro.entry, t, (const float*)d_in, a->D, whole ? d_log : nullptr,
                                  whole ? d_act : nullptr, flags, a->N, a->A, a->stream);
     };
     int b = ro.fill, t = ro.t;
@@ -492,10 +504,10 @@ static void mark(fi_actor* a, int i) {
     if (a->profiling) (void)hipEventRecord(a->ev[i], a->stream);
 }
 
-static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int32_t* actions, float* logits,
-               float* values) {
-    static const char* const names[] = {"actor_act_obs", "actor_act_frames", "actor_act_planes"};
-    const std::string nm = names[kind];
+// What every act call checks before anything is enqueued or pushed: the policy, the parameters and
+// a recording handle's refusals (fi_rollout.h). *completing: the (T+1)-th call of the unroll being filled.
+static int act_allowed(fi_actor* a, int kind, const void* in, const uint8_t* start, const std::string& nm,
+                       bool* completing) {
     FI_REQUIRE(a, nm + ": null actor");
     if (kind == IN_OBS)
         FI_REQUIRE(a->cfg.arch == FI_ARCH_MLP, nm + ": an Atari handle takes frames or planes (fi_actor_act_frames, "
@@ -505,19 +517,28 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     FI_REQUIRE(in && (kind != IN_PLANES || start), nm + ": null input");
     if (!a->have_params)
         return fail(FI_ERR_STATE, nm + ": no parameters yet (fi_actor_set_params with the learner's published blob)");
-    // a recording handle refuses before anything is enqueued or pushed
     const bool recording = a->ro.T > 0;
-    const bool completing = recording && a->ro.t == a->ro.T;  // the (T+1)-th call of the unroll being filled
+    *completing = recording && a->ro.t == a->ro.T;
     if (recording) {
         FI_REQUIRE(kind != IN_FRAMES, nm + ": the handle records a rollout, and stacked records are not produced "
                                            "(fi_actor_act_planes, or fi_rollout_end first)");
         if (a->ro.need_outcome)
             return fail(FI_ERR_STATE, nm + ": the previous step's rewards and discounts were never supplied "
                                            "(fi_rollout_outcome after every act call of a recording handle)");
-        if (completing && a->ro.ready >= 0)
+        if (*completing && a->ro.ready >= 0)
             return fail(FI_ERR_STATE, nm + ": this call completes an unroll, and the previous one has not been "
                                            "released: its buffer takes the next unroll's record 0 (fi_rollout_release)");
     }
+    return FI_OK;
+}
+
+static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int32_t* actions, float* logits,
+               float* values) {
+    static const char* const names[] = {"actor_act_obs", "actor_act_frames", "actor_act_planes"};
+    const std::string nm = names[kind];
+    bool completing = false;
+    FI_TRY(act_allowed(a, kind, in, start, nm, &completing));
+    const bool recording = a->ro.T > 0;
     FI_HIP_CHECK(hipSetDevice(a->dev));
     const size_t N = a->N, A = a->A;
     void* dst = nullptr;
@@ -545,7 +566,7 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     mark(a, PH_PUSH);
     if (kind == IN_PLANES) FI_TRY(push_planes_launch(a->stacks, a->planes, a->planes + N * kPlaneBytes, a->N, a->stream));
     mark(a, PH_FWD);
-    if (kind == IN_OBS) FI_TRY(mlp_forward(a, d_log, d_val));
+    if (kind == IN_OBS) FI_TRY(mlp_forward(a, a->obs, d_log, d_val));
     else FI_TRY(atari_forward(a->atari, kind == IN_PLANES ? a->stacks : a->frames, d_log, d_val, a->stream));
     mark(a, PH_SAMPLE);
     FI_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), a->stream));
@@ -555,9 +576,12 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     mark(a, PH_COUNT);
     a->draw++;
     FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    a->dev_pending = false;
     // after the outputs' copy and the wait for it: the record kernels sit in none of the profiled
     // phases and the caller does not wait for them
-    if (recording) FI_TRY(record_step(a, kind, completing, d_log, d_act));
+    if (recording)
+        FI_TRY(record_step(a, kind, completing, kind == IN_PLANES ? (const void*)a->planes : (const void*)a->obs,
+                           a->planes ? a->planes + N * kPlaneBytes : nullptr, d_log, d_act));
     if (a->profiling) {
         for (int p = 0; p < PH_COUNT; ++p) {
             float ms = 0.f;
@@ -587,6 +611,102 @@ extern "C" int fi_actor_act_frames(fi_actor* a, const uint8_t* frames, int32_t* 
 extern "C" int fi_actor_act_planes(fi_actor* a, const uint8_t* planes, const uint8_t* episode_start, int32_t* actions,
                                    float* logits, float* values) {
     return act(a, IN_PLANES, planes, episode_start, actions, logits, values);
+}
+
+// ------------------------------------------------------------------ the act call on device pointers (fi_env.h)
+int fi::check_dev_span(int dev, const void* p, size_t bytes, size_t align, const std::string& what) {
+    FI_REQUIRE(p, what + " is null");
+    FI_REQUIRE((uintptr_t)p % align == 0, what + " must be " + std::to_string(align) + "-byte aligned");
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != dev) {
+        (void)hipGetLastError();
+        return fail(FI_ERR_INVALID, what + " is not device memory of the handle's device " + std::to_string(dev));
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FI_ERR_INVALID, what + " lies in no device allocation");
+    }
+    const size_t have = size - (size_t)((const char*)p - (const char*)base);
+    FI_REQUIRE(bytes <= have, what + ": the allocation ends " + std::to_string(have) + " bytes behind the pointer, " +
+                                  std::to_string(bytes) + " are read");
+    return FI_OK;
+}
+
+// the event and the counter of the device calls, made by the first of them
+static int ensure_dev_calls(fi_actor* a) {
+    if (!a->dev_done) FI_HIP_CHECK(hipEventCreateWithFlags(&a->dev_done, hipEventDisableTiming));
+    if (!a->dev_bad) {
+        FI_TRY(dalloc(a, (void**)&a->dev_bad, sizeof(int)));
+        FI_HIP_CHECK(hipMemsetAsync(a->dev_bad, 0, sizeof(int), a->stream));
+    }
+    return FI_OK;
+}
+
+// act() without the copies and the wait: the same launches, on the caller's pointers
+static int act_dev(fi_actor* a, int kind, const void* in, const uint8_t* start, void* ready_event) {
+    const std::string nm = kind == IN_OBS ? "actor_act_obs_dev" : "actor_act_planes_dev";
+    bool completing = false;
+    FI_TRY(act_allowed(a, kind, in, start, nm, &completing));
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    const size_t N = a->N;
+    if (kind == IN_OBS) {
+        FI_TRY(check_dev_span(a->dev, in, N * a->D * sizeof(float), 16, nm + ": obs_dev"));
+    } else {
+        FI_TRY(check_dev_span(a->dev, in, N * kPlaneBytes, 16, nm + ": planes_dev"));
+        FI_TRY(check_dev_span(a->dev, start, N, 16, nm + ": episode_start_dev"));
+    }
+    FI_TRY(ensure_dev_calls(a));
+    int32_t* d_act = (int32_t*)a->out;
+    float* d_val = (float*)(a->out + a->off_val);
+    float* d_log = (float*)(a->out + a->off_log);
+    if (ready_event) FI_HIP_CHECK(hipStreamWaitEvent(a->stream, (hipEvent_t)ready_event, 0));
+    a->dev_pending = true;
+    if (kind == IN_PLANES) FI_TRY(push_planes_launch(a->stacks, (const uint8_t*)in, start, a->N, a->stream));
+    if (kind == IN_OBS) FI_TRY(mlp_forward(a, (const float*)in, d_log, d_val));
+    else FI_TRY(atari_forward(a->atari, a->stacks, d_log, d_val, a->stream));
+    // dev_bad is not zeroed here: it adds up until fi_actor_sync reads it
+    FI_TRY(sample_actions_launch(d_log, a->N, a->A, a->mode, a->seed, a->draw, d_act, a->dev_bad, a->stream));
+    a->draw++;
+    if (a->ro.T > 0) FI_TRY(record_step(a, kind, completing, in, start, d_log, d_act));
+    FI_HIP_CHECK(hipEventRecord(a->dev_done, a->stream));
+    return FI_OK;
+}
+
+extern "C" int fi_actor_act_planes_dev(fi_actor* a, const uint8_t* planes_dev, const uint8_t* episode_start_dev,
+                                       void* ready_event) {
+    return act_dev(a, IN_PLANES, planes_dev, episode_start_dev, ready_event);
+}
+extern "C" int fi_actor_act_obs_dev(fi_actor* a, const float* obs_dev, void* ready_event) {
+    return act_dev(a, IN_OBS, obs_dev, nullptr, ready_event);
+}
+
+extern "C" int fi_actor_outputs_dev(fi_actor* a, const int32_t** actions_dev, const float** logits_dev,
+                                    const float** values_dev, void** done_event) {
+    FI_REQUIRE(a, "actor_outputs_dev: null actor");
+    if (actions_dev) *actions_dev = (const int32_t*)a->out;
+    if (values_dev) *values_dev = (const float*)(a->out + a->off_val);
+    if (logits_dev) *logits_dev = (const float*)(a->out + a->off_log);
+    if (done_event) *done_event = (void*)a->dev_done;
+    return FI_OK;
+}
+
+extern "C" void* fi_actor_stream(fi_actor* a) { return a ? (void*)a->stream : nullptr; }
+
+extern "C" int fi_actor_sync(fi_actor* a, int64_t* nonfinite_rows) {
+    FI_REQUIRE(a, "actor_sync: null actor");
+    if (nonfinite_rows) *nonfinite_rows = 0;
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    int bad = 0;
+    if (a->dev_bad) FI_HIP_CHECK(hipMemcpyAsync(&bad, a->dev_bad, sizeof(int), hipMemcpyDeviceToHost, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    a->dev_pending = false;
+    if (bad == 0) return FI_OK;
+    FI_HIP_CHECK(hipMemsetAsync(a->dev_bad, 0, sizeof(int), a->stream));  // ahead of the next call's sampling
+    if (nonfinite_rows) *nonfinite_rows = bad;
+    return fail(FI_ERR_NONFINITE, "actor_sync: " + std::to_string(bad) + " rows held NaN / Inf logits in the device act "
+                                      "calls since the last sync (their action is 0)");
 }
 
 extern "C" int fi_actor_reset_stacks(fi_actor* a) {
@@ -702,7 +822,12 @@ extern "C" int fi_rollout_outcome(fi_actor* a, const float* rewards, const float
     if (!ro.need_outcome)
         return fail(FI_ERR_STATE, "rollout_outcome: no act call since the last outcome: every step takes one");
     FI_HIP_CHECK(hipSetDevice(a->dev));
-    // the pinned block is free: the act call between two outcomes has waited for the stream
+    // the pinned block is free: the act call between two outcomes has waited for the stream (a
+    // device act call has not: wait here)
+    if (a->dev_pending) {
+        FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+        a->dev_pending = false;
+    }
     const size_t N = a->N;
     std::memcpy(ro.pin_outcome, rewards, N * sizeof(float));
     std::memcpy(ro.pin_outcome + N, discounts, N * sizeof(float));
@@ -711,6 +836,29 @@ extern "C" int fi_rollout_outcome(fi_actor* a, const float* rewards, const float
     const size_t field = (size_t)ro.last_t * ro.rec + (atari ? kPlaneRecReward : kMlpRecReward);
     FI_TRY(scatter_outcome_launch(ro.buf[ro.last_buf], ro.entry, field, ro.outcome, a->N, a->stream));
     ro.need_outcome = false;
+    return FI_OK;
+}
+
+// fi_env.h: the same state machine, the scatter straight from the caller's device arrays
+extern "C" int fi_rollout_outcome_dev(fi_actor* a, const float* rewards_dev, const float* discounts_dev,
+                                      void* ready_event) {
+    FI_REQUIRE(a, "rollout_outcome_dev: null actor");
+    auto& ro = a->ro;
+    if (ro.T == 0) return fail(FI_ERR_STATE, "rollout_outcome_dev: the handle does not record (fi_rollout_begin)");
+    if (!ro.need_outcome)
+        return fail(FI_ERR_STATE, "rollout_outcome_dev: no act call since the last outcome: every step takes one");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    const size_t bytes = (size_t)a->N * sizeof(float);
+    FI_TRY(check_dev_span(a->dev, rewards_dev, bytes, 16, "rollout_outcome_dev: rewards_dev"));
+    FI_TRY(check_dev_span(a->dev, discounts_dev, bytes, 16, "rollout_outcome_dev: discounts_dev"));
+    FI_TRY(ensure_dev_calls(a));
+    if (ready_event) FI_HIP_CHECK(hipStreamWaitEvent(a->stream, (hipEvent_t)ready_event, 0));
+    a->dev_pending = true;
+    const bool atari = a->cfg.arch == FI_ARCH_ATARI;
+    const size_t field = (size_t)ro.last_t * ro.rec + (atari ? kPlaneRecReward : kMlpRecReward);
+    FI_TRY(scatter_outcome_launch(ro.buf[ro.last_buf], ro.entry, field, rewards_dev, discounts_dev, a->N, a->stream));
+    ro.need_outcome = false;
+    FI_HIP_CHECK(hipEventRecord(a->dev_done, a->stream));
     return FI_OK;
 }
 
@@ -762,10 +910,10 @@ extern "C" int fi_rollout_end(fi_actor* a) {
     return FI_OK;
 }
 
-// what fi_ring_push_rollout (ring.hip) compares with the ring
+// what fi_ring_push_rollout (ring.hip) compares with the ring, and fi_env_rollout (env.hip) with the environment
 int fi::actor_info(const fi_actor* a, ActorInfo* out) {
     FI_REQUIRE(a && out, "actor_info: null argument");
-    *out = ActorInfo{a->dev, a->N};
+    *out = ActorInfo{a->dev, a->N, a->cfg.arch, a->ro.T > 0, a->stream};
     return FI_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "fi_gather.h"
 #include "fi_learner.h"
 
@@ -142,6 +144,9 @@ int record_obs_launch(void* entries, size_t stride, int t, const float* obs, int
 // out: N rewards then N discounts; field: byte offset of the reward in entry 0 (the record's
 // offset plus the reward's in a record, records.h: the discount follows it)
 int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* out, int N, hipStream_t s);
+// the same from two arrays of N floats (fi_env.h: the rewards and discounts are in device memory already)
+int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* rewards, const float* discounts,
+                           int N, hipStream_t s);
 
 // learner.cpp: what fi_learner_step_rollout (actor.hip: it holds both handles) compares with the
 // actor. learner.cpp itself calls nothing of actor.hip, so a library of the learner alone links
@@ -163,10 +168,18 @@ int learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n
 int learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
                          bool wait, const char* who);
 
-// actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring
+// actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, and what fi_env_rollout
+// (env.hip) enqueues behind
 struct ActorInfo {
     int dev, N;
+    int arch;
+    bool recording;
+    hipStream_t stream;
 };
 int actor_info(const fi_actor* a, ActorInfo* out);
+// actor.hip: `bytes` from p on are device memory of device `dev` inside one allocation, and p is
+// `align`-byte aligned: the check of fi_learner_step_entries_dev for the pointers of fi_env.h.
+// FI_ERR_INVALID with `what` (call: argument) in the message
+int check_dev_span(int dev, const void* p, size_t bytes, size_t align, const std::string& what);
 
 }  // namespace fi

@@ -165,25 +165,33 @@ int record_obs_launch(void* entries, size_t stride, int t, const float* obs, int
 }
 
 // ---------------------------------------------------------------- rewards and discounts
-// N rows of two floats: out = rewards (N) then discounts (N); field = the byte offset of the
-// reward in the record (the discount follows it).
+// N rows of two floats, from the rewards (N) and the discounts (N): the host's staging block holds
+// one behind the other, a device environment (fi_env.h) two arrays of its own; field = the byte
+// offset of the reward in the record (the discount follows it).
 __global__ __launch_bounds__(256) void scatter_outcome_kernel(char* __restrict__ rec, size_t stride,
-                                                              const float* __restrict__ out, int N) {
+                                                              const float* __restrict__ rewards,
+                                                              const float* __restrict__ discounts, int N) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     float* __restrict__ f = (float*)(rec + (size_t)i * stride);
-    f[0] = out[i];
-    f[1] = out[N + i];
+    f[0] = rewards[i];
+    f[1] = discounts[i];
 }
 
-int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* out, int N, hipStream_t s) {
-    FI_REQUIRE(entries && out && N >= 1, "rollout_outcome: bad arguments");
+int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* rewards, const float* discounts,
+                           int N, hipStream_t s) {
+    FI_REQUIRE(entries && rewards && discounts && N >= 1, "rollout_outcome: bad arguments");
     FI_REQUIRE(((uintptr_t)entries + field) % 4 == 0 && stride % 4 == 0 && stride >= field + 8,
                "rollout_outcome: misaligned record");
     hipLaunchKernelGGL(scatter_outcome_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
-                       (char*)entries + field, stride, out, N);
+                       (char*)entries + field, stride, rewards, discounts, N);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
+}
+
+int scatter_outcome_launch(void* entries, size_t stride, size_t field, const float* out, int N, hipStream_t s) {
+    FI_REQUIRE(out && N >= 1, "rollout_outcome: bad arguments");
+    return scatter_outcome_launch(entries, stride, field, out, out + N, N, s);
 }
 
 }  // namespace fi

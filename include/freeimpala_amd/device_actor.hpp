@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fi_actor.h"
+#include "fi_env.h"
 #include "fi_gather.h"
 #include "fi_rollout.h"
 
@@ -123,6 +124,32 @@ public:
     bool end_rollout() { return ok(fi_rollout_end(h_)); }
     fi_actor* handle() { return h_; }
 
+    // Device pointers in, nothing waits (include/fi_env.h): the act call and the outcome are enqueued
+    // on the handle's stream behind ready_event (a hipEvent_t or nullptr) and read the caller's
+    // device memory; outputs_dev() names the handle's own output tensors and the event behind the
+    // last such call; sync() waits and reports the rows that held NaN / Inf logits since the last sync
+    // (false, with the count, when there were any).
+    struct DeviceOutputs {
+        const int32_t* actions = nullptr;  // N
+        const float* logits = nullptr;     // N * A
+        const float* values = nullptr;     // N
+        void* done_event = nullptr;
+    };
+    bool act_planes_dev(const uint8_t* planes_dev, const uint8_t* episode_start_dev, void* ready_event = nullptr) {
+        return ok(fi_actor_act_planes_dev(h_, planes_dev, episode_start_dev, ready_event));
+    }
+    bool act_obs_dev(const float* obs_dev, void* ready_event = nullptr) {
+        return ok(fi_actor_act_obs_dev(h_, obs_dev, ready_event));
+    }
+    bool outputs_dev(DeviceOutputs& out) {
+        return ok(fi_actor_outputs_dev(h_, &out.actions, &out.logits, &out.values, &out.done_event));
+    }
+    bool outcome_dev(const float* rewards_dev, const float* discounts_dev, void* ready_event = nullptr) {
+        return ok(fi_rollout_outcome_dev(h_, rewards_dev, discounts_dev, ready_event));
+    }
+    bool sync(int64_t* nonfinite_rows = nullptr) { return ok(fi_actor_sync(h_, nonfinite_rows)); }
+    void* stream() { return fi_actor_stream(h_); }  // hipStream_t
+
 private:
     void size(ActResult& out) const {
         out.actions.resize((size_t)cfg_.num_envs);
@@ -141,6 +168,55 @@ private:
 
     ActorConfig cfg_;
     fi_actor* h_ = nullptr;
+    std::string err_;
+};
+
+// The built-in device environment (include/fi_env.h: Catch on 84x84 planes, num_envs of them, their
+// state in device memory). rollout() enqueues n_steps of act -> step -> outcome on the actor's
+// stream and returns at once; steps_enqueued counts the steps before a refusal.
+class DeviceCatchEnv {
+public:
+    struct Tensors {
+        const uint8_t* planes = nullptr;         // N * 7056
+        const uint8_t* episode_start = nullptr;  // N
+        const float* rewards = nullptr;          // N
+        const float* discounts = nullptr;        // N
+    };
+
+    DeviceCatchEnv(int num_envs, float gamma, uint64_t seed, int device = 0) : n_(num_envs) {
+        if (fi_env_create(device, num_envs, gamma, seed, &h_) != FI_OK)
+            throw std::runtime_error(std::string("fi_env_create: ") + fi_last_error());
+    }
+    ~DeviceCatchEnv() { fi_env_destroy(h_); }
+    DeviceCatchEnv(const DeviceCatchEnv&) = delete;
+    DeviceCatchEnv& operator=(const DeviceCatchEnv&) = delete;
+
+    int num_envs() const { return n_; }
+    const std::string& last_error() const { return err_; }
+    bool step(const int32_t* actions_dev, void* ready_event = nullptr, void* stream = nullptr) {
+        return ok(fi_env_step(h_, actions_dev, ready_event, stream));
+    }
+    Tensors tensors() {
+        Tensors t;
+        fi_env_tensors(h_, &t.planes, &t.episode_start, &t.rewards, &t.discounts);
+        return t;
+    }
+    void* stepped_event() { return fi_env_stepped_event(h_); }
+    bool stats(uint64_t& episodes, int64_t& return_sum) { return ok(fi_env_stats(h_, &episodes, &return_sum)); }
+    bool rollout(DeviceActor& actor, int n_steps, int32_t* steps_enqueued = nullptr) {
+        return ok(fi_env_rollout(h_, actor.handle(), n_steps, steps_enqueued));
+    }
+    fi_env* handle() { return h_; }
+
+private:
+    bool ok(int rc) {
+        if (rc == FI_OK) return true;
+        err_ = fi_last_error();
+        return false;
+    }
+
+    int n_;
+    fi_env* h_ = nullptr;
     std::string err_;
 };
 
