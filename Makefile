@@ -7,9 +7,9 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/env.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
-HDRS := $(wildcard $(CSRC)/*.h) include/fi_learner.h include/fi_farmer.h include/fi_actor.h include/fi_rollout.h include/fi_gather.h include/fi_ring.h include/fi_prio.h include/fi_env.h
+HDRS := $(wildcard $(CSRC)/*.h) include/fi_learner.h include/fi_farmer.h include/fi_actor.h include/fi_rollout.h include/fi_gather.h include/fi_ring.h include/fi_prio.h include/fi_weights.h include/fi_env.h
 
 all: $(LIBDIR)/libfi_learner.so oracle host tools
 

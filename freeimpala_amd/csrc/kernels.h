@@ -54,6 +54,11 @@ constexpr int kHeadsFusedGrid = 512;
 int f32_heads_bwd_fused(const HeadsGrad& g, const float* h2, const float* Wh, int H, float* dz2, float* slab,
                         float* cs_slab, int grid, hipStream_t s);
 
+// weights.hip: dlog (T, B, A) and the first T rows of dval times w[b] in place (include/fi_weights.h).
+// learner.cpp takes it as a pointer, as it takes the ingests below
+int scale_columns_launch(float* dlog, float* dval, const float* w, int T, int B, int A, hipStream_t s);
+typedef int (*ScaleFn)(float* dlog, float* dval, const float* w, int T, int B, int A, hipStream_t s);
+
 // misc.hip
 int colsum_partial(const float* Y, int M, int N, int splits, float* slab, hipStream_t s);
 int heads_colsum_partial(const HeadsGrad& g, int splits, float* slab, hipStream_t s);
@@ -153,6 +158,7 @@ int scatter_outcome_launch(void* entries, size_t stride, size_t field, const flo
 struct LearnerInfo {
     int dev, arch, B, A, D, T;
     bool dev_entries_ok;  // MLP, or Atari in the planes format
+    bool column_weights;  // fi_learner_set_column_weights holds (fi_weights.h)
 };
 int learner_info(const fi_learner* l, LearnerInfo* out);
 
@@ -164,9 +170,16 @@ typedef int (*IngestFn)(const void* ctx, const BatchTensors& to);
 int learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out, bool wait,
                           const char* who, IngestFn ingest);
 // the step from a source that writes the column table itself (fi_ring.h: ring.hip has checked the
-// ring against learner_info()); the learner's stream waits for `ready` (nullable) first
+// ring against learner_info()); the learner's stream waits for `ready` (nullable) first. weights
+// (nullable): B floats in device memory that the ingest writes, the step's column weights in place
+// of the handle's (fi_weights.h: a prioritised step's importance weights), applied by `scale`
 int learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
-                         bool wait, const char* who);
+                         bool wait, const char* who, const float* weights = nullptr, ScaleFn scale = nullptr);
+// learner.cpp: the handle's column weights (fi_weights.h; the C entry points are weights.hip's, which
+// hands its launcher in: learner.cpp names nothing of weights.hip)
+int learner_set_column_weights(fi_learner* l, const float* w_host, int32_t n, ScaleFn scale);
+int learner_clear_column_weights(fi_learner* l);
+int learner_column_weights(fi_learner* l, float* dst, int32_t n);
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, and what fi_env_rollout
 // (env.hip) enqueues behind

@@ -102,6 +102,10 @@ struct fi_learner {
     const void** cols = nullptr;
     uint32_t* versions = nullptr;
     bool have_versions = false;
+    // per-column loss weights (fi_weights.h): B floats, allocated by the first set
+    float* col_w = nullptr;
+    bool col_w_on = false;
+    ScaleFn col_scale = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -610,6 +614,8 @@ struct BatchSource {
     const void* ctx;
     hipEvent_t done;  // recorded behind the ingest: ingest_done[slot], or entries_consumed
     bool versions;    // the ingest fills the version block
+    const float* weights;  // nullable: column weights the ingest writes, in place of the handle's (fi_weights.h)
+    ScaleFn scale;         // what applies them
 };
 
 static BatchTensors batch_tensors(const fi_learner* l) {
@@ -648,6 +654,13 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
                              l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue,
                              l->small, l->vt_ws, l->vt_ws_bytes, l->stream, false, &vt_nblk,
                              l->bad));
+    }
+    // the loss is a plain sum over the columns: w_b times column b's gradient is the gradient of
+    // sum_b w_b L_b (fi_weights.h). vs, pg_adv and the loss partials stay unweighted
+    const bool own = src && src->weights && src->scale;
+    if (const float* w = own ? src->weights : (l->col_w_on ? l->col_w : nullptr)) {
+        Tag t(l, "scale_columns");
+        FI_TRY((own ? src->scale : l->col_scale)(l->dlogits, l->dvalue, w, l->T, l->B, l->A, l->stream));
     }
     mark(l, FI_PHASE_BACKWARD);
     BucketAllReduce bar(l);
@@ -876,7 +889,8 @@ static int ingest_entries(const void* ctx, const BatchTensors& to) {
 static int step_staged_slot(fi_learner* l, fi_step_stats* out, bool wait) {
     const int s = l->cur;
     const Entries e{l->rec_slot[s], l->rec_entry_bytes, l->rec_format};
-    return finish_step(l, BatchSource{&l->h2d_done[s], 1, ingest_entries, &e, l->ingest_done[s], false}, out, wait);
+    return finish_step(l, BatchSource{&l->h2d_done[s], 1, ingest_entries, &e, l->ingest_done[s], false, nullptr, nullptr},
+                       out, wait);
 }
 
 extern "C" int fi_learner_step(fi_learner* l, const void* const* entries, size_t n_entries,
@@ -1001,7 +1015,7 @@ static int step_entries_dev(fi_learner* l, const void* entries, size_t stride, v
         FI_TRY(ensure_entries_consumed(l));
         const hipEvent_t ev = (hipEvent_t)ready;
         const Entries e{entries, stride, l->rec_format};
-        return finish_step(l, BatchSource{&ev, 1, ingest_entries, &e, l->entries_consumed, false}, out, wait);
+        return finish_step(l, BatchSource{&ev, 1, ingest_entries, &e, l->entries_consumed, false, nullptr, nullptr}, out, wait);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }
@@ -1026,7 +1040,7 @@ extern "C" size_t fi_learner_staging_bytes(const fi_learner* l) { return l ? 4 *
 // still links (as with actor.hip above).
 // the column table and the version block on first use, then the step, waited for or enqueued only
 static int step_gathered(fi_learner* l, const hipEvent_t* ready, int n_ready, IngestFn ingest, const void* ctx,
-                         fi_step_stats* out, bool wait) {
+                         fi_step_stats* out, bool wait, const float* weights = nullptr, ScaleFn scale = nullptr) {
     FI_HIP_CHECK(hipSetDevice(l->dev));
     if (!l->cols) {
         void* p = nullptr;
@@ -1035,7 +1049,8 @@ static int step_gathered(fi_learner* l, const hipEvent_t* ready, int n_ready, In
         l->versions = (uint32_t*)((char*)p + 8 * (size_t)l->B);
     }
     FI_TRY(ensure_entries_consumed(l));
-    return finish_step(l, BatchSource{ready, n_ready, ingest, ctx, l->entries_consumed, true}, out, wait);
+    return finish_step(l, BatchSource{ready, n_ready, ingest, ctx, l->entries_consumed, true, weights, scale},
+                       out, wait);
 }
 
 int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out,
@@ -1071,12 +1086,12 @@ int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32
 }
 
 int fi::learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
-                             bool wait, const char* who) {
+                             bool wait, const char* who, const float* weights, ScaleFn scale) {
     try {
         const std::string nm = who;
         FI_REQUIRE(l && ingest, nm + ": null argument");
         FI_TRY(require_dev_entries(l, nm));
-        return step_gathered(l, &ready, 1, ingest, ctx, out, wait);
+        return step_gathered(l, &ready, 1, ingest, ctx, out, wait, weights, scale);
     } catch (const std::exception& e) {
         return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
     }
@@ -1101,7 +1116,46 @@ extern "C" int fi_learner_batch_versions(fi_learner* l, fi_batch_versions* out) 
 // what fi_learner_step_rollout (actor.hip: it needs both handles) compares with the actor
 int fi::learner_info(const fi_learner* l, LearnerInfo* out) {
     FI_REQUIRE(l && out, "learner_info: null argument");
-    *out = LearnerInfo{l->dev, l->cfg.arch, l->B, l->A, l->D, l->T, dev_entries_ok(l)};
+    *out = LearnerInfo{l->dev, l->cfg.arch, l->B, l->A, l->D, l->T, dev_entries_ok(l), l->col_w_on};
+    return FI_OK;
+}
+
+// ------------------------------------------------------------------ per-column loss weights (fi_weights.h)
+// The C entry points are weights.hip's: it hands its launcher in, as gather.hip and ring.hip hand in
+// their ingests, so a library of the learner alone still links.
+int fi::learner_set_column_weights(fi_learner* l, const float* w_host, int32_t n, ScaleFn scale) {
+    FI_REQUIRE(l && w_host && scale, "set_column_weights: null argument");
+    FI_REQUIRE(n == l->B, "set_column_weights: n = " + std::to_string(n) + " != the learner's batch " + std::to_string(l->B));
+    for (int32_t i = 0; i < n; ++i)
+        FI_REQUIRE(std::isfinite(w_host[i]) && w_host[i] >= 0.f, "set_column_weights: weight " + std::to_string(w_host[i]) +
+                                                                     " at index " + std::to_string(i) +
+                                                                     " is negative or not finite");
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    if (!l->col_w) FI_TRY(dalloc_n(l, &l->col_w, (size_t)l->B));
+    // behind every step enqueued so far, which may still read the old weights
+    FI_HIP_CHECK(hipMemcpyAsync(l->col_w, w_host, 4 * (size_t)n, hipMemcpyHostToDevice, l->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+    l->col_scale = scale;
+    l->col_w_on = true;
+    return FI_OK;
+}
+
+int fi::learner_clear_column_weights(fi_learner* l) {
+    FI_REQUIRE(l, "clear_column_weights: null learner");
+    l->col_w_on = false;
+    return FI_OK;
+}
+
+int fi::learner_column_weights(fi_learner* l, float* dst, int32_t n) {
+    FI_REQUIRE(l && dst, "column_weights: null argument");
+    FI_REQUIRE(n == l->B, "column_weights: n = " + std::to_string(n) + " != the learner's batch " + std::to_string(l->B));
+    if (!l->col_w_on) {
+        for (int32_t i = 0; i < n; ++i) dst[i] = 1.f;
+        return FI_OK;
+    }
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    FI_HIP_CHECK(hipMemcpyAsync(dst, l->col_w, 4 * (size_t)n, hipMemcpyDeviceToHost, l->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(l->stream));
     return FI_OK;
 }
 

@@ -6,6 +6,7 @@
 //   * prio_columns_kernel: takes ring_columns_kernel's place -- one wave per column; a replayed
 //     column scans the chunk sums, then the 1,024 priorities of the chunk its number falls into
 //   * prio_from_td_kernel: a column's priority from vs and values, quantised
+//   * prio_from_td_alpha_kernel: the same with the exponent alpha on it (fi_weights.h)
 //   * prio_clear_kernel / prio_max_kernel: the refresh's two passes
 // The rule (fi_prio.h) is integer arithmetic from the quantised priorities on: q >= 1, capacity
 // <= 2^20, so every sum is below 2^51 and exact in u64, and (x * Q) >> 64 with a 64-bit x picks
@@ -20,6 +21,7 @@
 
 #include "fi_common.h"
 #include "fi_prio.h"
+#include "fi_weights.h"
 #include "kernels.h"
 #include "ring_handle.h"
 
@@ -212,10 +214,8 @@ __device__ __forceinline__ uint32_t quantize(float p) {
 
 // One lane per column; the loads of one t are contiguous over the wave, the tensors being (T, B).
 // The sum runs over t ascending. A NaN difference makes sum and maximum NaN. Reads 8 T B bytes.
-__global__ __launch_bounds__(256) void prio_from_td_kernel(const float* __restrict__ vs, const float* __restrict__ values,
-                                                           int T, int B, float eta, uint32_t* __restrict__ q_out) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
+__device__ __forceinline__ float td_priority(const float* __restrict__ vs, const float* __restrict__ values, int T, int B,
+                                             int b, float eta) {
     float sum = 0.f, mx = 0.f;
     for (int t = 0; t < T; ++t) {
         const size_t i = (size_t)t * B + b;
@@ -223,16 +223,37 @@ __global__ __launch_bounds__(256) void prio_from_td_kernel(const float* __restri
         sum += d;
         mx = (d > mx || d != d) ? d : mx;
     }
-    q_out[b] = quantize(eta * mx + (1.f - eta) * (sum / (float)T));
+    return eta * mx + (1.f - eta) * (sum / (float)T);
 }
 
+__global__ __launch_bounds__(256) void prio_from_td_kernel(const float* __restrict__ vs, const float* __restrict__ values,
+                                                           int T, int B, float eta, uint32_t* __restrict__ q_out) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    q_out[b] = quantize(td_priority(vs, values, T, B, b, eta));
+}
+
+// The table holds p^alpha (fi_weights.h); launched for alpha != 1 only. powf(NaN, 0) is 1, so NaN is
+// taken out first.
+__global__ __launch_bounds__(256) void prio_from_td_alpha_kernel(const float* __restrict__ vs,
+                                                                 const float* __restrict__ values, int T, int B, float eta,
+                                                                 float alpha, uint32_t* __restrict__ q_out) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float p = td_priority(vs, values, T, B, b, eta);
+    q_out[b] = p != p ? kQMax : quantize(powf(p, alpha));
+}
+
+// alpha == 1: fi_prio.h's kernel, as before fi_weights.h
 static int prio_from_td_launch(const float* vs, const float* values, int T, int B, float eta, uint32_t* q_out,
-                               hipStream_t s) {
+                               hipStream_t s, float alpha = 1.f) {
     FI_REQUIRE(vs && values && q_out, "prio_from_td: null argument");
     FI_REQUIRE(T >= 1 && B >= 1, "prio_from_td: T = " + std::to_string(T) + ", B = " + std::to_string(B) + " must be >= 1");
     FI_REQUIRE(eta >= 0.f && eta <= 1.f, "prio_from_td: eta " + std::to_string(eta) + " outside [0, 1]");
-    hipLaunchKernelGGL(prio_from_td_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, vs, values, T, B, eta,
-                       q_out);
+    FI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "prio_from_td: alpha " + std::to_string(alpha) + " outside [0, 1]");
+    const dim3 grid((unsigned)((B + 255) / 256));
+    if (alpha == 1.f) hipLaunchKernelGGL(prio_from_td_kernel, grid, dim3(256), 0, s, vs, values, T, B, eta, q_out);
+    else hipLaunchKernelGGL(prio_from_td_alpha_kernel, grid, dim3(256), 0, s, vs, values, T, B, eta, alpha, q_out);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -274,14 +295,20 @@ struct PrioBatch {
     uint64_t* sums;
     uint64_t fill_first, fill_count;
     uint32_t q_init;
+    float beta;
+    float* is_w;  // nullable: the step's importance weights (fi_weights.h); null: none are computed
 };
 
 // what a learner's prioritised step from a ring enqueues as its ingest (learner.cpp:
-// learner_step_columns): the q_init fill, then the draw, then the gathering ingest
+// learner_step_columns): the q_init fill, then the draw, the importance weights where the step has
+// any, then the gathering ingest
 static int learner_prio_ingest(const void* ctx, const BatchTensors& to) {
     const PrioBatch& pb = *(const PrioBatch*)ctx;
     FI_TRY(prio_init_launch(pb.table, pb.rb.C, pb.fill_first, pb.fill_count, pb.q_init, to.stream));
     FI_TRY(prio_columns_launch(pb.rb, pb.table, pb.sums, to.cols, to.B, to.versions, to.stream));
+    if (pb.is_w)
+        FI_TRY(prio_is_weights_launch(pb.rb.entries_out, to.B, pb.rb.n_fresh, pb.table, pb.rb.C, pb.rb.lo, pb.rb.n_valid,
+                                      pb.sums, pb.beta, pb.is_w, to.stream));
     return gather_ingest(to);
 }
 
@@ -407,6 +434,9 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
     FI_REQUIRE(!r->prio_owner || r->prio_owner == l,
                nm + ": a second learner handle: this ring's priorities belong to the learner that took its first "
                     "prioritised step");
+    if (r->beta > 0.f && li.column_weights)
+        return fail(FI_ERR_STATE, nm + ": beta = " + std::to_string(r->beta) + " and the learner has column weights set: "
+                                       "one source of weights per step (fi_learner_clear_column_weights, or beta = 0)");
     void *vs = nullptr, *values = nullptr;
     size_t vs_bytes = 0, values_bytes = 0;
     FI_TRY(fi_learner_tensor(l, "vs", &vs, &vs_bytes));
@@ -429,6 +459,26 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
         }
         r->prio_q_cap = li.B;
     }
+    // importance weights: with beta == 0 or no replayed column nothing is computed or launched
+    const bool weighted = r->beta > 0.f && n_fresh < li.B;
+    if (weighted && r->is_w_cap < li.B) {
+        if (r->is_w) {
+            FI_HIP_CHECK(hipEventSynchronize(r->prio_done));  // behind the last step that read it
+            (void)hipFree(r->is_w);
+            r->is_w = nullptr;
+            r->is_w_cap = 0;
+            r->is_w_valid = false;
+        }
+        const hipError_t e = hipMalloc((void**)&r->is_w, 4 * (size_t)li.B);
+        if (e != hipSuccess) {
+            r->is_w = nullptr;
+            (void)hipGetLastError();
+            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(4 * (size_t)li.B) + ") for the importance weights");
+        }
+        r->is_w_cap = li.B;
+    }
+    pb.beta = r->beta;
+    pb.is_w = weighted ? r->is_w : nullptr;
     pb.rb.entries_out = r->last;
     pb.table = r->prio;
     pb.sums = r->prio_sums;
@@ -436,10 +486,15 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
     const uint64_t filled = pb.rb.tail + (uint64_t)n_fresh;
     pb.fill_first = r->prio_hi > pb.rb.lo ? r->prio_hi : pb.rb.lo;
     pb.fill_count = filled > pb.fill_first ? filled - pb.fill_first : 0;
-    const int rc = learner_step_columns(l, r->have_pushed ? r->pushed : nullptr, learner_prio_ingest, &pb, out, wait, who);
+    const int rc = learner_step_columns(l, r->have_pushed ? r->pushed : nullptr, learner_prio_ingest, &pb, out, wait, who,
+                                        pb.is_w, scale_columns_launch);
     // after any other status the counters stay and nothing is refreshed; a fill that was enqueued
     // wrote q_init to entries at or above prio_hi only, which read as q_init anyway
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
+    if (rc != FI_OK && rc != FI_ERR_NONFINITE) {
+        if (weighted) r->is_w_valid = false;  // the weights buffer may have been rewritten
+        return rc;
+    }
+    r->is_w_valid = weighted;
     std::string why;
     if (rc != FI_OK) why = fi_last_error();  // the launchers below leave it alone unless they fail
     if (filled > r->prio_hi) r->prio_hi = filled;
@@ -447,7 +502,7 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
     // the refresh, behind the step on the learner's stream: r->last was written by the draw in front
     // of it on the same stream
     hipStream_t s = (hipStream_t)fi_learner_stream(l);
-    FI_TRY(prio_from_td_launch((const float*)vs, (const float*)values, li.T, li.B, r->eta, r->prio_q, s));
+    FI_TRY(prio_from_td_launch((const float*)vs, (const float*)values, li.T, li.B, r->eta, r->prio_q, s, r->alpha));
     FI_TRY(prio_scatter_launch(r->prio, r->C, r->last, r->prio_q, li.B, s));
     FI_HIP_CHECK(hipEventRecord(r->prio_done, s));
     r->have_prio_done = true;
@@ -467,6 +522,11 @@ extern "C" int fi_learner_step_ring_prioritized_async(fi_learner* l, fi_ring* r,
 extern "C" int fi_prio_from_td(const float* vs, const float* values, int32_t T, int32_t B, float eta, uint32_t* q_out,
                                void* stream) {
     return prio_from_td_launch(vs, values, T, B, eta, q_out, (hipStream_t)stream);
+}
+
+extern "C" int fi_prio_from_td_alpha(const float* vs, const float* values, int32_t T, int32_t B, float eta, float alpha,
+                                     uint32_t* q_out, void* stream) {
+    return prio_from_td_launch(vs, values, T, B, eta, q_out, (hipStream_t)stream, alpha);
 }
 
 extern "C" int fi_prio_scatter(uint32_t* table, int64_t capacity, const uint64_t* entries, const uint32_t* q_cols,

@@ -132,6 +132,7 @@ static void destroy(fi_ring* r) {
     (void)hipSetDevice(r->dev);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     if (r->have_prio_done) (void)hipEventSynchronize(r->prio_done);  // behind the last refresh (fi_prio.h)
+    if (r->is_w) (void)hipFree(r->is_w);  // fi_weights.h
     if (r->prio_q) (void)hipFree(r->prio_q);
     if (r->prio_sums) (void)hipFree(r->prio_sums);
     if (r->prio) (void)hipFree(r->prio);

@@ -36,6 +36,11 @@ struct fi_ring {
     const fi_learner* prio_owner = nullptr;  // the learner whose stream touches the table
     hipEvent_t prio_done = nullptr;          // behind the last prioritised step's refresh
     bool have_prio_done = false;
+    // ---- exponents and importance weights (fi_weights.h); the values after fi_prio_enable
+    float alpha = 1.f, beta = 0.f;
+    float* is_w = nullptr;    // the weights of the last prioritised step that computed any, 4 * is_w_cap bytes
+    int is_w_cap = 0;
+    bool is_w_valid = false;  // the last prioritised step computed weights
 };
 
 namespace fi {
@@ -58,5 +63,9 @@ int ring_step_entries(fi_ring* r, int B, const std::string& nm);
 // ring.hip: what follows a step that ran (rc: FI_OK or FI_ERR_NONFINITE) or was enqueued: the ring's
 // stream waits for the consumed event, the counters move; returns rc with its message restored
 int ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B, int rc);
+// weights.hip: the importance weights of a prioritised step (fi_weights.h), behind the draw that wrote
+// `entries` and the chunk sums on the same stream
+int prio_is_weights_launch(const uint64_t* entries, int B, int n_fresh, const uint32_t* table, int64_t C, uint64_t lo,
+                           uint64_t n_valid, const uint64_t* sums, float beta, float* w_out, hipStream_t s);
 
 }  // namespace fi

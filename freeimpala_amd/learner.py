@@ -210,6 +210,18 @@ class DeviceLearner:
         check(ring_mod.lib().fi_learner_step_ring(self._h, ring._h, n, C.byref(st)), "fi_learner_step_ring")
         return st.as_dict()
 
+    # --- per-column loss weights (include/fi_weights.h)
+    def set_column_weights(self, w) -> None:
+        """(B,) finite weights >= 0: every later step's loss is sum_b w_b L_b, on every path, until
+        ``set_column_weights(None)`` clears them. The reported losses stay the unweighted sums."""
+        from . import weights
+        weights.set_column_weights(self, w)
+
+    def column_weights(self) -> np.ndarray:
+        """(B,) float32: the weights that hold; all 1 when none are set."""
+        from . import weights
+        return weights.column_weights(self)
+
     def step_segments_dev(self, segments, stats: bool = True) -> dict:
         """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum
         to the batch; segment k fills the next n columns once its event (or None) has completed."""

@@ -74,10 +74,10 @@ def quantize_priority(p):
     return int(q) if q.ndim == 0 else q
 
 
-def td_priorities(vs, values, eta: float):
-    """(B,) int64: the quantised priority of every column from vs (T, B) and values (>= T rows, B)
-    as the device holds them, computed in fp64: p = eta * max_t d + (1 - eta) * mean_t d with
-    d = |vs - values|. eta is taken as the fp32 number the ring holds."""
+def td_magnitudes(vs, values, eta: float) -> np.ndarray:
+    """(B,) float64: p = eta * max_t d + (1 - eta) * mean_t d with d = |vs - values|, from vs (T, B)
+    and values (>= T rows, B) as the device holds them, computed in fp64; NaN for a column with a NaN
+    difference. eta is taken as the fp32 number the ring holds."""
     vs = np.asarray(vs, np.float32).astype(np.float64)
     T = vs.shape[0]
     v = np.asarray(values, np.float32).astype(np.float64)[:T]
@@ -86,8 +86,13 @@ def td_priorities(vs, values, eta: float):
         d = np.abs(vs - v)
         nan = np.isnan(d).any(axis=0)
         p = eta * np.where(np.isnan(d), 0.0, d).max(axis=0) + (1.0 - eta) * d.sum(axis=0) / T
-        p = np.where(nan, np.nan, p)
-    return quantize_priority(p)
+        return np.where(nan, np.nan, p)
+
+
+def td_priorities(vs, values, eta: float):
+    """(B,) int64: the quantised priority of every column from vs (T, B) and values (>= T rows, B)
+    as the device holds them, computed in fp64 (td_magnitudes)."""
+    return quantize_priority(td_magnitudes(vs, values, eta))
 
 
 def prio_batch_entries(philox4, seed: int, draw: int, B: int, n_fresh: int, head: int, tail: int, capacity: int,

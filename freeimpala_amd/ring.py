@@ -166,6 +166,24 @@ class EntryRing:
         from . import prio
         prio.write(self, first_entry, q)
 
+    # --- exponents and importance weights (include/fi_weights.h; weights.py)
+    def set_priority_exponents(self, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """alpha in [0, 1]: later refreshes store p^alpha. beta in [0, 1]: later prioritised steps weigh
+        every replayed column's loss by (n_valid q / Q)^-beta over the batch's maximum."""
+        from . import weights
+        weights.set_exponents(self, alpha, beta)
+
+    def priority_exponents(self) -> dict:
+        """dict(alpha, beta, weights_valid)."""
+        from . import weights
+        return weights.exponents(self)
+
+    def last_weights(self, B: int) -> np.ndarray:
+        """(B,) float32: the importance weights of the last prioritised step (B: that learner's batch);
+        all 1 when it computed none."""
+        from . import weights
+        return weights.last_weights(self, B)
+
     def close(self) -> None:
         if self._h:
             lib().fi_ring_destroy(self._h)
