@@ -82,9 +82,21 @@ int reduce_slabs(float* slab, int splits, size_t count, float* out, hipStream_t 
 int grad_sqnorm(const float* g, size_t n, double* part, int nblk, double* out, hipStream_t s,
                 const double* vt_part = nullptr, int vt_nblk = 0, double* vt_losses = nullptr,
                 int* nonfinite = nullptr);
+// RMSProp's hyper-parameters (include/fi_train.h): opt == FI_TRAIN_OPT_RMSPROP takes them from rms
+struct RmsPropHp {
+    float decay, momentum, eps;
+    bool eps_in_sqrt;
+};
 int optimizer_step(int opt, float* p, const float* g, float* m, float* v, size_t n, float lr,
                    float b1, float b2, float eps, double bc1, double bc2, const double* sqnorm,
-                   float max_norm, hipStream_t s, int* skip = nullptr);  // skip: int[4], see misc.hip
+                   float max_norm, hipStream_t s, int* skip = nullptr,  // skip: int[4], see misc.hip
+                   const RmsPropHp* rms = nullptr);
+// one RMSProp update: the mean square in v, the momentum buffer in m (not touched, and nullable,
+// when hp.momentum == 0); 16 bytes per lane when every pointer is 16-byte aligned
+int rmsprop_step(float* p, const float* g, float* v, float* m, size_t n, float lr, const RmsPropHp& hp,
+                 const double* sqnorm, float max_norm, hipStream_t s, int* skip = nullptr);
+// r[i] clamped to [-c, c] in place, NaN kept
+int clip_rewards_launch(float* r, size_t n, float c, hipStream_t s);
 int to_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t s);
 int fill_hash_bf16(void* dst, size_t n, uint32_t seed, hipStream_t s);
 int synth_launch(uint64_t seed, int T, int B, int B_glob, int b_off, int A, int D, float gamma,

@@ -25,6 +25,7 @@
 #include "atari.h"
 #include "fi_common.h"
 #include "fi_rollout.h"
+#include "fi_train.h"
 #include "kernels.h"
 
 namespace fi {
@@ -106,6 +107,14 @@ struct fi_learner {
     float* col_w = nullptr;
     bool col_w_on = false;
     ScaleFn col_scale = nullptr;
+    // the training recipe (fi_train.h): configuration, not part of the state blob
+    int opt_kind = FI_OPT_ADAM;  // cfg.optimizer until fi_train_set_rmsprop
+    RmsPropHp rms{0.f, 0.f, 0.f, false};
+    float lr_base = 0.f;  // cfg.lr until fi_train_set_lr
+    float lr_end = 0.f;
+    uint64_t lr_steps = 0;
+    bool lr_sched = false;
+    float reward_clip = 0.f;  // 0: off
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -265,6 +274,8 @@ static int create(const fi_learner_config* cfg, fi_learner** out) {
     } guard{l};
 
     l->cfg = *cfg;
+    l->opt_kind = cfg->optimizer;
+    l->lr_base = cfg->lr;
     l->dev = cfg->device;
     l->T = cfg->seq_len;
     l->B = cfg->batch;
@@ -618,6 +629,15 @@ struct BatchSource {
     ScaleFn scale;         // what applies them
 };
 
+// the learning rate of the update numbered s >= 1 (fi_train.h): lr_base, or the linear anneal from
+// lr_base at s = 1 to lr_end at s = lr_steps + 1 and beyond, in double
+static float lr_of(const fi_learner* l, uint64_t s) {
+    if (!l->lr_sched) return l->lr_base;
+    const uint64_t k = std::min(s - 1, l->lr_steps);
+    if (k == l->lr_steps) return l->lr_end;  // exactly, whatever (x * n) / n rounds to
+    return (float)((double)l->lr_base + ((double)l->lr_end - (double)l->lr_base) * (double)k / (double)l->lr_steps);
+}
+
 static BatchTensors batch_tensors(const fi_learner* l) {
     return BatchTensors{l->cfg.arch, l->T,   l->B,    l->A,   l->D,    l->obs,      l->frames, l->mu,
                         l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
@@ -638,6 +658,10 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         }
         FI_HIP_CHECK(hipEventRecord(src->done, l->stream));
         if (src->versions) l->have_versions = true;
+    }
+    if (l->reward_clip > 0.f) {  // in place and idempotent: a resident batch stepped again is clipped once in effect
+        Tag t(l, "clip_rewards");
+        FI_TRY(clip_rewards_launch(l->rew, (size_t)l->TB, l->reward_clip, l->stream));
     }
     mark(l, FI_PHASE_FORWARD);
     if (l->cfg.arch == FI_ARCH_MLP) FI_TRY(mlp_forward(l));
@@ -688,9 +712,10 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     const double bc2 = 1.0 - std::pow((double)l->cfg.beta2, step);
     {
         Tag t(l, "optimizer");
-        FI_TRY(optimizer_step(l->cfg.optimizer, l->params, l->grads, l->opt_m, l->opt_v, l->nparams,
-                              l->cfg.lr, l->cfg.beta1, l->cfg.beta2, l->cfg.eps, bc1, bc2,
-                              l->small + 3, l->cfg.max_grad_norm, l->stream, l->bad));
+        // the rate of update `step` (fi_train.h) travels by value: an enqueued step keeps it
+        FI_TRY(optimizer_step(l->opt_kind, l->params, l->grads, l->opt_m, l->opt_v, l->nparams,
+                              lr_of(l, (uint64_t)step), l->cfg.beta1, l->cfg.beta2, l->cfg.eps, bc1, bc2,
+                              l->small + 3, l->cfg.max_grad_norm, l->stream, l->bad, &l->rms));
     }
     if (l->atari) {
         Tag t(l, "weights_bf16");
@@ -1157,6 +1182,96 @@ int fi::learner_column_weights(fi_learner* l, float* dst, int32_t n) {
     FI_HIP_CHECK(hipMemcpyAsync(dst, l->col_w, 4 * (size_t)n, hipMemcpyDeviceToHost, l->stream));
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
     return FI_OK;
+}
+
+// ------------------------------------------------------------------ the training recipe (fi_train.h)
+static int check_rmsprop(const char* who, float decay, float momentum, float eps) {
+    const std::string w = who;
+    FI_REQUIRE(decay >= 0.f && decay < 1.f, w + ": decay " + std::to_string(decay) + " outside [0, 1)");
+    FI_REQUIRE(momentum >= 0.f && momentum < 1.f, w + ": momentum " + std::to_string(momentum) + " outside [0, 1)");
+    FI_REQUIRE(std::isfinite(eps) && eps > 0.f, w + ": eps " + std::to_string(eps) + " is not positive and finite");
+    return FI_OK;
+}
+
+extern "C" int fi_train_set_rmsprop(fi_learner* l, float decay, float momentum, float eps, int eps_in_sqrt) {
+    FI_REQUIRE(l, "train_set_rmsprop: null learner");
+    FI_TRY(check_rmsprop("train_set_rmsprop", decay, momentum, eps));
+    if (l->step_count != 0 || l->in_flight)
+        return fail(FI_ERR_STATE, "train_set_rmsprop: an update has been enqueued (step_count " +
+                                      std::to_string(l->step_count) + (l->in_flight ? ", a step in flight" : "") +
+                                      "): choose the optimiser before the first step");
+    l->rms = RmsPropHp{decay, momentum, eps, eps_in_sqrt != 0};
+    l->opt_kind = FI_TRAIN_OPT_RMSPROP;
+    return FI_OK;
+}
+
+extern "C" int fi_train_set_lr(fi_learner* l, float lr) {
+    FI_REQUIRE(l, "train_set_lr: null learner");
+    FI_REQUIRE(std::isfinite(lr) && lr >= 0.f, "train_set_lr: lr " + std::to_string(lr) + " is negative or not finite");
+    l->lr_base = lr;
+    return FI_OK;
+}
+
+extern "C" int fi_train_set_lr_schedule(fi_learner* l, float lr_end, uint64_t n_steps) {
+    FI_REQUIRE(l, "train_set_lr_schedule: null learner");
+    FI_REQUIRE(std::isfinite(lr_end) && lr_end >= 0.f,
+               "train_set_lr_schedule: lr_end " + std::to_string(lr_end) + " is negative or not finite");
+    FI_REQUIRE(n_steps >= 1, "train_set_lr_schedule: n_steps 0 (at least 1)");
+    l->lr_end = lr_end;
+    l->lr_steps = n_steps;
+    l->lr_sched = true;
+    return FI_OK;
+}
+
+extern "C" int fi_train_clear_lr_schedule(fi_learner* l) {
+    FI_REQUIRE(l, "train_clear_lr_schedule: null learner");
+    l->lr_sched = false;
+    return FI_OK;
+}
+
+extern "C" int fi_train_set_reward_clip(fi_learner* l, float c) {
+    FI_REQUIRE(l, "train_set_reward_clip: null learner");
+    FI_REQUIRE(std::isfinite(c) && c >= 0.f, "train_set_reward_clip: c " + std::to_string(c) +
+                                                 " is negative or not finite (0 turns the clip off)");
+    l->reward_clip = c;
+    return FI_OK;
+}
+
+extern "C" int fi_train_get_state(fi_learner* l, fi_train_state* out) {
+    FI_REQUIRE(l && out, "train_get_state: null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->optimizer = (uint32_t)l->opt_kind;
+    out->eps_in_sqrt = l->rms.eps_in_sqrt ? 1u : 0u;
+    out->decay = l->rms.decay;
+    out->momentum = l->rms.momentum;
+    out->eps = l->rms.eps;
+    out->lr_base = l->lr_base;
+    out->lr_end = l->lr_end;
+    out->next_update = (uint64_t)l->step_count + 1;
+    out->lr_next = lr_of(l, out->next_update);
+    out->reward_clip = l->reward_clip;
+    out->schedule_on = l->lr_sched ? 1u : 0u;
+    out->lr_steps = l->lr_steps;
+    return FI_OK;
+}
+
+extern "C" int fi_train_rmsprop_update(float* p, const float* g, float* v, float* m, size_t n, float lr, float decay,
+                                       float momentum, float eps, int eps_in_sqrt, const double* sqnorm_dev,
+                                       float max_norm, int* skip_dev, void* stream) {
+    FI_REQUIRE(p && g && v && n >= 1, "train_rmsprop_update: null argument or n = 0");
+    FI_TRY(check_rmsprop("train_rmsprop_update", decay, momentum, eps));
+    FI_REQUIRE(m || momentum == 0.f, "train_rmsprop_update: momentum " + std::to_string(momentum) + " needs m");
+    FI_REQUIRE(std::isfinite(lr) && lr >= 0.f, "train_rmsprop_update: lr " + std::to_string(lr) + " is negative or not finite");
+    FI_REQUIRE(sqnorm_dev || !(max_norm > 0.f), "train_rmsprop_update: max_norm " + std::to_string(max_norm) + " needs sqnorm_dev");
+    FI_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)v | (uintptr_t)m) % 4 == 0, "train_rmsprop_update: pointers must be 4-byte aligned");
+    return rmsprop_step(p, g, v, m, n, lr, RmsPropHp{decay, momentum, eps, eps_in_sqrt != 0}, sqnorm_dev, max_norm,
+                        (hipStream_t)stream, skip_dev);
+}
+
+extern "C" int fi_train_clip_rewards(float* r, size_t n, float c, void* stream) {
+    FI_REQUIRE(r && n >= 1 && (uintptr_t)r % 4 == 0, "train_clip_rewards: null or misaligned r, or n = 0");
+    FI_REQUIRE(std::isfinite(c) && c > 0.f, "train_clip_rewards: c " + std::to_string(c) + " is not positive and finite");
+    return clip_rewards_launch(r, n, c, (hipStream_t)stream);
 }
 
 extern "C" int fi_learner_synth_batch(fi_learner* l, uint64_t seed, int32_t b_global,

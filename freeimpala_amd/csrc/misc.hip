@@ -4,10 +4,12 @@
 //     Atari records with their 84x84x4 frames, and the single-plane Atari records whose
 //     4-frame stack is rebuilt): the kernels of ingest_kernels.h on entries a fixed stride apart
 //   * column sums / split-K slab reduction (deterministic, fixed order)
-//   * global gradient norm, Adam / SGD with global-norm clipping, fp32 -> bf16
+//   * global gradient norm, Adam / SGD / RMSProp with global-norm clipping, fp32 -> bf16
+//   * the reward clamp in front of V-trace (include/fi_train.h)
 #include <algorithm>
 
 #include "fi_common.h"
+#include "fi_train.h"
 #include "ingest_kernels.h"
 #include "kernels.h"
 
@@ -397,9 +399,123 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, s
         p[i] -= lr * (g[i] * scale);
 }
 
+// RMSProp (include/fi_train.h), fp32, element by element; scale and the skip flags as adam_kernel's.
+//   g' = g scale;  v = decay v + (1 - decay) g' g';  d = sqrtf(v + eps) or sqrtf(v) + eps
+//   kMom: m = momentum m + g' / d, p -= lr m;  otherwise p -= lr g' / d and m is never touched
+// HBM-bound: 20 bytes per element without momentum, 28 with. A lane moves 16 bytes of each stream
+// per access, every load of a quad issued before its first store; the n4 whole quads go by grid
+// stride and the n mod 4 elements behind them one lane each. n4 = 0 (a pointer off a 16-byte
+// boundary) sends every element down the scalar loop: the same arithmetic, the same bits.
+template <bool kMom, bool kEpsInSqrt>
+__device__ __forceinline__ void rmsprop_one(float& p, float g, float& v, float& m, float scale, float lr, float decay,
+                                            float momentum, float eps) {
+    const float gs = g * scale;
+    const float vi = decay * v + (1.0f - decay) * gs * gs;
+    v = vi;
+    const float d = kEpsInSqrt ? sqrtf(vi + eps) : sqrtf(vi) + eps;
+    const float u = gs / d;
+    if (kMom) {
+        const float mi = momentum * m + u;
+        m = mi;
+        p -= lr * mi;
+    } else {
+        p -= lr * u;
+    }
+}
+
+template <bool kMom, bool kEpsInSqrt>
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ v, float* __restrict__ m, size_t n,
+                                                      size_t n4, float lr, float decay, float momentum, float eps,
+                                                      const double* sqnorm, float max_norm, int* skip) {
+    if (skip_update(skip)) return;
+    float scale = 1.f;
+    if (max_norm > 0.f) {
+        const double norm = sqrt(*sqnorm);
+        if (norm > max_norm) scale = (float)((double)max_norm / (norm + 1e-6));
+    }
+    const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    float4* __restrict__ p4 = (float4*)p;
+    const float4* __restrict__ g4 = (const float4*)g;
+    float4* __restrict__ v4 = (float4*)v;
+    float4* __restrict__ m4 = (float4*)m;
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 pi = p4[i], vi = v4[i], mi = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gi = g4[i];
+        if (kMom) mi = m4[i];
+        rmsprop_one<kMom, kEpsInSqrt>(pi.x, gi.x, vi.x, mi.x, scale, lr, decay, momentum, eps);
+        rmsprop_one<kMom, kEpsInSqrt>(pi.y, gi.y, vi.y, mi.y, scale, lr, decay, momentum, eps);
+        rmsprop_one<kMom, kEpsInSqrt>(pi.z, gi.z, vi.z, mi.z, scale, lr, decay, momentum, eps);
+        rmsprop_one<kMom, kEpsInSqrt>(pi.w, gi.w, vi.w, mi.w, scale, lr, decay, momentum, eps);
+        v4[i] = vi;
+        if (kMom) m4[i] = mi;
+        p4[i] = pi;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) {  // the tail, one element per lane
+        float pi = p[i], vi = v[i], mi = 0.f;
+        if (kMom) mi = m[i];
+        rmsprop_one<kMom, kEpsInSqrt>(pi, g[i], vi, mi, scale, lr, decay, momentum, eps);
+        v[i] = vi;
+        if (kMom) m[i] = mi;
+        p[i] = pi;
+    }
+}
+
+static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
+
+int rmsprop_step(float* p, const float* g, float* v, float* m, size_t n, float lr, const RmsPropHp& hp,
+                 const double* sqnorm, float max_norm, hipStream_t s, int* skip) {
+    const bool mom = hp.momentum > 0.f;
+    const bool vec = aligned16(p) && aligned16(g) && aligned16(v) && (!mom || aligned16(m));
+    const size_t n4 = vec ? n / 4 : 0;
+    const dim3 grid(grid_for(vec ? n4 + (n & 3) : n)), block(256);
+#define FI_RMS(MOM, EIS)                                                                                          \
+    hipLaunchKernelGGL((rmsprop_kernel<MOM, EIS>), grid, block, 0, s, p, g, v, m, n, n4, lr, hp.decay, hp.momentum, \
+                       hp.eps, sqnorm, max_norm, skip)
+    if (mom) {
+        if (hp.eps_in_sqrt) FI_RMS(true, true);
+        else FI_RMS(true, false);
+    } else {
+        if (hp.eps_in_sqrt) FI_RMS(false, true);
+        else FI_RMS(false, false);
+    }
+#undef FI_RMS
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+// r clamped to [-c, c] in place (include/fi_train.h), by comparison: a NaN stays a NaN, -0.0 stays
+// -0.0, +-Inf becomes +-c. 16 bytes per lane over the n4 whole quads, the tail one element per lane
+__device__ __forceinline__ float clip_one(float r, float c) { return r > c ? c : (r < -c ? -c : r); }
+
+__global__ __launch_bounds__(256) void clip_rewards_kernel(float* __restrict__ r, size_t n, size_t n4, float c) {
+    const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    float4* __restrict__ r4 = (float4*)r;
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 x = r4[i];
+        x.x = clip_one(x.x, c);
+        x.y = clip_one(x.y, c);
+        x.z = clip_one(x.z, c);
+        x.w = clip_one(x.w, c);
+        r4[i] = x;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) r[i] = clip_one(r[i], c);
+}
+
+int clip_rewards_launch(float* r, size_t n, float c, hipStream_t s) {
+    const size_t n4 = aligned16(r) ? n / 4 : 0;
+    hipLaunchKernelGGL(clip_rewards_kernel, dim3(grid_for(n4 ? n4 + (n & 3) : n)), dim3(256), 0, s, r, n, n4, c);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
 int optimizer_step(int opt, float* p, const float* g, float* m, float* v, size_t n, float lr,
                    float b1, float b2, float eps, double bc1, double bc2, const double* sqnorm,
-                   float max_norm, hipStream_t s, int* skip) {
+                   float max_norm, hipStream_t s, int* skip, const RmsPropHp* rms) {
+    if (opt == FI_TRAIN_OPT_RMSPROP) {
+        if (!rms) return fail(FI_ERR_INVALID, "optimizer_step: RMSProp without its hyper-parameters");
+        return rmsprop_step(p, g, v, m, n, lr, *rms, sqnorm, max_norm, s, skip);
+    }
     if (opt == FI_OPT_ADAM)
         hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1,
                            b2, eps, bc1, bc2, sqnorm, max_norm, skip);

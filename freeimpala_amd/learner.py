@@ -55,12 +55,14 @@ class DeviceLearner:
         self.D, self.H = obs_dim, hidden
         self.arch = arch
         self.records = records
-        if records == "planes":  # host entries carry single planes
-            try:
+        try:
+            if records == "planes":  # host entries carry single planes
                 self.set_record_format(_abi.FI_RECORDS_PLANES)
-            except Exception:
-                self.close()
-                raise
+            if optimizer == "rmsprop":  # created as "sgd" is, then switched (include/fi_train.h)
+                self.set_rmsprop()
+        except Exception:
+            self.close()
+            raise
 
     # --- sizes
     @property
@@ -221,6 +223,45 @@ class DeviceLearner:
         """(B,) float32: the weights that hold; all 1 when none are set."""
         from . import weights
         return weights.column_weights(self)
+
+    # --- the training recipe (include/fi_train.h)
+    def set_rmsprop(self, decay: float = 0.99, momentum: float = 0.0, eps: float = 0.01,
+                    eps_in_sqrt: bool = False) -> None:
+        """Switch the handle to RMSProp, before its first step (the defaults are monobeast's). The
+        mean square lives in "adam_v" and the momentum buffer in "adam_m"."""
+        from . import train
+        check(train.lib().fi_train_set_rmsprop(self._h, decay, momentum, eps, int(bool(eps_in_sqrt))),
+              "fi_train_set_rmsprop")
+
+    def set_lr(self, lr: float) -> None:
+        """Replace the base learning rate; between any two steps."""
+        from . import train
+        check(train.lib().fi_train_set_lr(self._h, lr), "fi_train_set_lr")
+
+    def set_lr_schedule(self, lr_end: float, n_steps: int) -> None:
+        """Anneal linearly from the base rate at update 1 to lr_end at update n_steps + 1 and beyond
+        (``train.lr_at``)."""
+        from . import train
+        if n_steps < 0:
+            raise ValueError(f"n_steps {n_steps} is negative")
+        check(train.lib().fi_train_set_lr_schedule(self._h, lr_end, n_steps), "fi_train_set_lr_schedule")
+
+    def clear_lr_schedule(self) -> None:
+        from . import train
+        check(train.lib().fi_train_clear_lr_schedule(self._h), "fi_train_clear_lr_schedule")
+
+    def set_reward_clip(self, c: float) -> None:
+        """Clamp the rewards of every later step to [-c, c] on the device, in front of V-trace; 0: off."""
+        from . import train
+        check(train.lib().fi_train_set_reward_clip(self._h, c), "fi_train_set_reward_clip")
+
+    def train_state(self) -> dict:
+        """fi_train_get_state as a dict: the optimiser and its numbers, the schedule, ``lr_next`` and
+        ``next_update`` (the rate and the number the next enqueued update gets), the reward clip."""
+        from . import train
+        st = train.TrainState()
+        check(train.lib().fi_train_get_state(self._h, C.byref(st)), "fi_train_get_state")
+        return st.as_dict()
 
     def step_segments_dev(self, segments, stats: bool = True) -> dict:
         """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum

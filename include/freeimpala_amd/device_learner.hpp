@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "fi_learner.h"
+#include "fi_train.h"
 
 namespace freeimpala_amd {
 
@@ -48,7 +49,17 @@ struct LearnerConfig {
     int num_actions = 18;      // --num-actions
     int obs_dim = 128;         // --obs-dim
     int hidden = 256;          // --hidden
-    std::string optimizer = "adam";  // --optimizer adam|sgd
+    std::string optimizer = "adam";  // --optimizer adam|sgd|rmsprop
+    // the training recipe (fi_train.h), applied to every handle right after fi_learner_create (so a
+    // --starting-model resume loads its state behind it); the defaults change nothing
+    float rms_decay = 0.99f;       // --rms-decay      (--optimizer rmsprop; monobeast's numbers)
+    float rms_momentum = 0.f;      // --rms-momentum
+    float rms_eps = 0.01f;         // --rms-eps
+    bool rms_eps_in_sqrt = false;  // --rms-eps-in-sqrt 0|1 (1: sqrt(v + eps), TensorFlow / the paper)
+    bool lr_schedule = false;      // --lr-end and --lr-steps, both or neither: anneal --lr linearly
+    float lr_end = 0.f;            //   to --lr-end over --lr-steps updates
+    uint64_t lr_steps = 0;
+    float reward_clip = 0.f;       // --reward-clip c: rewards clamped to [-c, c] before V-trace (0: off)
     std::string publish = "fp32";    // --publish fp32|bf16
     float lr = 5e-4f;          // --lr  (reference README.md:112 default)
     float max_grad_norm = 40.f;      // --max-grad-norm
@@ -94,6 +105,7 @@ struct LearnerConfig {
             if (!v[0] || (end && *end)) throw std::invalid_argument("bad value for " + f + ": " + v);
             return x;
         };
+        bool have_end = false, have_steps = false;
         for (int i = 1; i + 1 < argc; ++i) {
             const std::string f = argv[i];
             const char* v = argv[i + 1];
@@ -114,6 +126,13 @@ struct LearnerConfig {
             else if (f == "--gamma") c.gamma = (float)num(f, v);
             else if (f == "--seed") c.seed = (uint64_t)num(f, v);
             else if (f == "--data-parallel") c.data_parallel = (size_t)num(f, v);
+            else if (f == "--rms-decay") c.rms_decay = (float)num(f, v);
+            else if (f == "--rms-momentum") c.rms_momentum = (float)num(f, v);
+            else if (f == "--rms-eps") c.rms_eps = (float)num(f, v);
+            else if (f == "--rms-eps-in-sqrt") c.rms_eps_in_sqrt = num(f, v) != 0;
+            else if (f == "--lr-end") { c.lr_end = (float)num(f, v); have_end = true; }
+            else if (f == "--lr-steps") { c.lr_steps = steps_of(num(f, v)); have_steps = true; }
+            else if (f == "--reward-clip") c.reward_clip = (float)num(f, v);
             else if (f == "--devices") {
                 c.devices.clear();
                 std::string s = v;
@@ -146,11 +165,31 @@ struct LearnerConfig {
                     : "--entry-size must be >= " + std::to_string(c.min_entry_size()) + " = " +
                           c.min_entry_size_formula() + " for --learner-arch " + c.arch +
                           (c.planes() ? " --atari-records planes" : ""));
-        if (c.optimizer != "adam" && c.optimizer != "sgd") throw std::invalid_argument("--optimizer: adam|sgd");
+        if (c.optimizer != "adam" && c.optimizer != "sgd" && c.optimizer != "rmsprop")
+            throw std::invalid_argument("--optimizer: adam|sgd|rmsprop");
+        if (have_end != have_steps) throw std::invalid_argument("--lr-end and --lr-steps go together: both or neither");
+        if (have_end) c.lr_schedule = true;
+        c.check_recipe();
         if (c.publish != "fp32" && c.publish != "bf16") throw std::invalid_argument("--publish: fp32|bf16");
         if (c.data_parallel == 0 || c.batch_size % c.data_parallel != 0)
             throw std::invalid_argument("--data-parallel must divide --batch-size");
         return c;
+    }
+
+    // --lr-steps as an integer >= 1 (checked before the cast: a negative double has no uint64_t)
+    static uint64_t steps_of(double x) {
+        if (!(x >= 1.0 && x < 1.8e19)) throw std::invalid_argument("--lr-steps must be >= 1");
+        return (uint64_t)x;
+    }
+
+    // the ranges fi_train.h's setters accept, so a bad flag fails at the command line
+    void check_recipe() const {
+        if (!(rms_decay >= 0.f && rms_decay < 1.f)) throw std::invalid_argument("--rms-decay must be in [0, 1)");
+        if (!(rms_momentum >= 0.f && rms_momentum < 1.f)) throw std::invalid_argument("--rms-momentum must be in [0, 1)");
+        if (!(rms_eps > 0.f && rms_eps <= 3.4e38f)) throw std::invalid_argument("--rms-eps must be positive and finite");
+        if (lr_schedule && !(lr_end >= 0.f && lr_end <= 3.4e38f && lr_steps >= 1))
+            throw std::invalid_argument("--lr-end must be >= 0 and finite, --lr-steps >= 1");
+        if (!(reward_clip >= 0.f && reward_clip <= 3.4e38f)) throw std::invalid_argument("--reward-clip must be >= 0 and finite");
     }
 
     // Learner flags through a strict parser (freeimpala_amd::ArgumentParser or the argparse
@@ -188,6 +227,19 @@ struct LearnerConfig {
         c.gamma = (float)num("--gamma", str("--gamma"));
         c.seed = (uint64_t)num("--learner-seed", str("--learner-seed"));
         c.data_parallel = (size_t)num("--data-parallel", str("--data-parallel"));
+        c.rms_decay = (float)num("--rms-decay", str("--rms-decay"));
+        c.rms_momentum = (float)num("--rms-momentum", str("--rms-momentum"));
+        c.rms_eps = (float)num("--rms-eps", str("--rms-eps"));
+        c.rms_eps_in_sqrt = num("--rms-eps-in-sqrt", str("--rms-eps-in-sqrt")) != 0;
+        c.reward_clip = (float)num("--reward-clip", str("--reward-clip"));
+        // "" (the default): not given
+        const std::string end = str("--lr-end"), steps = str("--lr-steps");
+        if (end.empty() != steps.empty()) throw std::invalid_argument("--lr-end and --lr-steps go together: both or neither");
+        if (!end.empty()) {
+            c.lr_end = (float)num("--lr-end", end);
+            c.lr_steps = steps_of(num("--lr-steps", steps));
+            c.lr_schedule = true;
+        }
         const char* argv[] = {"", "--devices", nullptr};
         const std::string dev = str("--devices");
         argv[2] = dev.c_str();
@@ -210,7 +262,8 @@ struct LearnerConfig {
         k.num_actions = num_actions;
         k.obs_dim = obs_dim;
         k.hidden = hidden;
-        k.optimizer = optimizer == "sgd" ? FI_OPT_SGD : FI_OPT_ADAM;
+        // rmsprop: created as sgd is, then switched by fi_train_set_rmsprop
+        k.optimizer = optimizer == "sgd" || optimizer == "rmsprop" ? FI_OPT_SGD : FI_OPT_ADAM;
         k.publish_dtype = publish == "bf16" ? FI_PUBLISH_BF16 : FI_PUBLISH_FP32;
         k.device = devices[(p * data_parallel + g) % devices.size()];
         k.gamma = gamma;
@@ -238,7 +291,17 @@ void add_learner_arguments(Parser& program) {
     program.add_argument("--num-actions").help("Number of actions A").default_value(std::to_string(d.num_actions));
     program.add_argument("--obs-dim").help("MLP observation width (<= 128)").default_value(std::to_string(d.obs_dim));
     program.add_argument("--hidden").help("MLP hidden width").default_value(std::to_string(d.hidden));
-    program.add_argument("--optimizer").help("adam | sgd").default_value(d.optimizer);
+    program.add_argument("--optimizer").help("adam | sgd | rmsprop").default_value(d.optimizer);
+    program.add_argument("--rms-decay").help("RMSProp: decay of the mean square").default_value(std::string("0.99"));
+    program.add_argument("--rms-momentum").help("RMSProp: momentum (0: none)").default_value(std::string("0"));
+    program.add_argument("--rms-eps").help("RMSProp: epsilon").default_value(std::string("0.01"));
+    program.add_argument("--rms-eps-in-sqrt").help("RMSProp: 0 = sqrt(v) + eps (torch), 1 = sqrt(v + eps) (TensorFlow)")
+        .default_value(std::string("0"));
+    program.add_argument("--lr-end").help("Anneal --lr linearly to this rate over --lr-steps updates (with --lr-steps)")
+        .default_value(std::string(""));
+    program.add_argument("--lr-steps").help("Updates the linear anneal takes (with --lr-end)").default_value(std::string(""));
+    program.add_argument("--reward-clip").help("Clamp rewards to [-c, c] before V-trace (0: off)")
+        .default_value(std::string("0"));
     program.add_argument("--publish").help("Published weights dtype: fp32 | bf16").default_value(d.publish);
     program.add_argument("--lr").help("Learning rate").default_value(std::string("0.0005"));
     program.add_argument("--max-grad-norm").help("Global-norm gradient clip (<= 0: off)")
@@ -271,6 +334,12 @@ public:
                 if (cfg.planes() && fi_learner_set_record_format(shards_[p][g], FI_RECORDS_PLANES) != FI_OK) {
                     const std::string msg = std::string("fi_learner_set_record_format(player ") + std::to_string(p) +
                                             ", shard " + std::to_string(g) + "): " + fi_last_error();
+                    release();
+                    throw std::runtime_error(msg);
+                }
+                if (!apply_recipe(shards_[p][g])) {
+                    const std::string msg = std::string("training recipe (player ") + std::to_string(p) + ", shard " +
+                                            std::to_string(g) + "): " + fi_last_error();
                     release();
                     throw std::runtime_error(msg);
                 }
@@ -399,6 +468,16 @@ public:
     const LearnerConfig& config() const { return cfg_; }
 
 private:
+    // the fi_train.h calls the configuration asks for; none with the defaults
+    bool apply_recipe(fi_learner* h) const {
+        if (cfg_.optimizer == "rmsprop" &&
+            fi_train_set_rmsprop(h, cfg_.rms_decay, cfg_.rms_momentum, cfg_.rms_eps, cfg_.rms_eps_in_sqrt ? 1 : 0) != FI_OK)
+            return false;
+        if (cfg_.lr_schedule && fi_train_set_lr_schedule(h, cfg_.lr_end, cfg_.lr_steps) != FI_OK) return false;
+        if (cfg_.reward_clip > 0.f && fi_train_set_reward_clip(h, cfg_.reward_clip) != FI_OK) return false;
+        return true;
+    }
+
     // --data-parallel: contiguous shards of the M entries, one per device, stepped
     // concurrently (the in-step all-reduce needs every rank); loss sums added over the shards
     bool step_sharded(size_t p, const std::vector<const void*>& ptrs, size_t eb) {
