@@ -1,6 +1,9 @@
 // env.hip -- fi_env: Catch on 84x84 planes, N environments whose whole state lives in device
 // memory, behind the C ABI of include/fi_env.h (the rule is stated there), and fi_env_rollout,
-// which enqueues a whole unroll of a recording actor on its stream without a host wait.
+// which enqueues a whole unroll of a recording actor on its stream without a host wait. The handle
+// (env_handle.h) has a kind: what is not Catch's own here -- create, step, tensors, stats, read_state,
+// rollout -- serves a Breakout handle too (include/fi_breakout.h) and launches breakout.hip's kernels
+// for it; a Catch handle launches exactly the three kernels below.
 //
 // A step is two launches. env_update_kernel, one lane per environment, moves the paddle and the
 // ball, resets finished episodes and writes the step's scalars; env_render_kernel then draws every
@@ -13,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "env_handle.h"
 #include "fi_common.h"
 #include "fi_env.h"
 #include "kernels.h"
@@ -146,21 +150,7 @@ static int env_render_launch(const void* state, uint8_t* planes, int N, hipStrea
 
 using namespace fi;
 
-// ------------------------------------------------------------------ the handle
-struct fi_env {
-    int dev = 0, N = 0;
-    float gamma = 0.f;
-    uint64_t seed = 0;
-    char* block = nullptr;  // state | planes | episode_start | rewards | discounts | totals, each 256-byte aligned
-    uint4* state = nullptr;
-    uint8_t* planes = nullptr;
-    uint8_t* start = nullptr;
-    float* rewards = nullptr;
-    float* discounts = nullptr;
-    unsigned long long* totals = nullptr;
-    hipEvent_t stepped = nullptr;  // behind the last step's render
-};
-
+// ------------------------------------------------------------------ the handle (env_handle.h)
 static void destroy(fi_env* e) {
     if (!e) return;
     if (e->stepped) {
@@ -171,17 +161,33 @@ static void destroy(fi_env* e) {
     delete e;
 }
 
-static int create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, fi_env** out) {
-    FI_REQUIRE(out, "env_create: null argument");
+// the first state of a handle and a step's update, by kind
+static int init_launch(fi_env* e, hipStream_t s) {
+    if (e->kind == FI_ENV_BREAKOUT)
+        return breakout_init_launch(e->state, e->N, e->seed, e->start, e->rewards, e->discounts, s);
+    hipLaunchKernelGGL(env_init_kernel, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, s, e->state, e->N, e->seed,
+                       e->start, e->rewards, e->discounts);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+static int render_launch(fi_env* e, hipStream_t s) {
+    if (e->kind == FI_ENV_BREAKOUT) return breakout_render_launch(e->state, e->planes, e->N, s);
+    return env_render_launch(e->state, e->planes, e->N, s);
+}
+
+static int create(int kind, int32_t device, int32_t num_envs, float gamma, uint64_t seed, int32_t max_steps,
+                  const std::string& nm, fi_env** out) {
+    FI_REQUIRE(out, nm + ": null argument");
     *out = nullptr;
-    FI_REQUIRE(num_envs >= 1 && num_envs <= 0x7fffffff / kPlanePieces, "env_create: 1 <= num_envs <= 4869582");
-    FI_REQUIRE(gamma >= 0.f && gamma <= 1.f, "env_create: gamma outside [0, 1]");
+    FI_REQUIRE(num_envs >= 1 && num_envs <= 0x7fffffff / kPlanePieces, nm + ": 1 <= num_envs <= 4869582");
+    FI_REQUIRE(gamma >= 0.f && gamma <= 1.f, nm + ": gamma outside [0, 1]");
     int ndev = 0;
     FI_HIP_CHECK(hipGetDeviceCount(&ndev));
-    FI_REQUIRE(device >= 0 && device < ndev, "env_create: no such HIP device");
+    FI_REQUIRE(device >= 0 && device < ndev, nm + ": no such HIP device");
     FI_HIP_CHECK(hipSetDevice(device));
     fi_env* e = new (std::nothrow) fi_env();
-    FI_REQUIRE(e, "env_create: out of host memory");
+    FI_REQUIRE(e, nm + ": out of host memory");
     struct Guard {
         fi_env* e;
         bool ok = false;
@@ -191,15 +197,18 @@ static int create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, 
     e->N = num_envs;
     e->gamma = gamma;
     e->seed = seed;
+    e->kind = kind;
+    e->max_steps = max_steps;
+    e->state_words = kind == FI_ENV_BREAKOUT ? 8 : 4;
     const size_t N = (size_t)num_envs;
-    const size_t o_planes = round_up(N * sizeof(uint4)), o_start = o_planes + round_up(N * kPlaneBytes),
+    const size_t o_planes = round_up(N * (size_t)e->state_words * 4), o_start = o_planes + round_up(N * kPlaneBytes),
                  o_rew = o_start + round_up(N), o_disc = o_rew + round_up(N * sizeof(float)),
                  o_tot = o_disc + round_up(N * sizeof(float)), bytes = o_tot + kAlign;
     const hipError_t err = hipMalloc((void**)&e->block, bytes);
     if (err != hipSuccess) {
         e->block = nullptr;
         (void)hipGetLastError();
-        return fail(FI_ERR_OOM, "env_create: hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(err));
+        return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(err));
     }
     e->state = (uint4*)e->block;
     e->planes = (uint8_t*)(e->block + o_planes);
@@ -209,10 +218,8 @@ static int create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, 
     e->totals = (unsigned long long*)(e->block + o_tot);
     FI_HIP_CHECK(hipEventCreateWithFlags(&e->stepped, hipEventDisableTiming));
     FI_HIP_CHECK(hipMemsetAsync(e->block, 0, bytes, nullptr));
-    hipLaunchKernelGGL(env_init_kernel, dim3((unsigned)((num_envs + 255) / 256)), dim3(256), 0, nullptr, e->state,
-                       num_envs, seed, e->start, e->rewards, e->discounts);
-    FI_HIP_CHECK(hipGetLastError());
-    FI_TRY(env_render_launch(e->state, e->planes, num_envs, nullptr));
+    FI_TRY(init_launch(e, nullptr));
+    FI_TRY(render_launch(e, nullptr));
     FI_HIP_CHECK(hipEventRecord(e->stepped, nullptr));
     FI_HIP_CHECK(hipStreamSynchronize(nullptr));
     guard.ok = true;
@@ -220,12 +227,17 @@ static int create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, 
     return FI_OK;
 }
 
-extern "C" int fi_env_create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, fi_env** out) {
+int fi::env_create_handle(int kind, int32_t device, int32_t num_envs, float gamma, uint64_t seed, int32_t max_steps,
+                          const char* nm, fi_env** out) {
     try {
-        return create(device, num_envs, gamma, seed, out);
+        return create(kind, device, num_envs, gamma, seed, max_steps, nm, out);
     } catch (const std::exception& ex) {
-        return fail(FI_ERR_OOM, std::string("env_create: ") + ex.what());
+        return fail(FI_ERR_OOM, std::string(nm) + ": " + ex.what());
     }
+}
+
+extern "C" int fi_env_create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, fi_env** out) {
+    return env_create_handle(FI_ENV_CATCH, device, num_envs, gamma, seed, 0, "env_create", out);
 }
 
 extern "C" void fi_env_destroy(fi_env* e) {
@@ -238,8 +250,12 @@ extern "C" int32_t fi_env_num_envs(const fi_env* e) { return e ? e->N : 0; }
 
 // the step's two launches and the event, on s; the caller has checked the actions
 static int enqueue_step(fi_env* e, const int32_t* actions, hipStream_t s) {
-    FI_TRY(env_update_launch(e->state, actions, e->N, e->gamma, e->seed, e->start, e->rewards, e->discounts, e->totals, s));
-    FI_TRY(env_render_launch(e->state, e->planes, e->N, s));
+    if (e->kind == FI_ENV_BREAKOUT)
+        FI_TRY(breakout_update_launch(e->state, actions, e->N, e->gamma, e->seed, e->max_steps, e->start, e->rewards,
+                                      e->discounts, e->totals, s));
+    else
+        FI_TRY(env_update_launch(e->state, actions, e->N, e->gamma, e->seed, e->start, e->rewards, e->discounts, e->totals, s));
+    FI_TRY(render_launch(e, s));
     FI_HIP_CHECK(hipEventRecord(e->stepped, s));
     return FI_OK;
 }
@@ -269,13 +285,14 @@ extern "C" int fi_env_read_state(fi_env* e, int32_t* r, int32_t* c, int32_t* p, 
     FI_HIP_CHECK(hipSetDevice(e->dev));
     FI_HIP_CHECK(hipEventSynchronize(e->stepped));
     try {
-        std::vector<uint4> s((size_t)e->N);
-        FI_HIP_CHECK(hipMemcpy(s.data(), e->state, s.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+        const size_t W = (size_t)e->state_words;  // words 0-3 are r, c, p, k in every kind
+        std::vector<uint32_t> s((size_t)e->N * W);
+        FI_HIP_CHECK(hipMemcpy(s.data(), e->state, s.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (int i = 0; i < e->N; ++i) {
-            if (r) r[i] = (int32_t)s[i].x;
-            if (c) c[i] = (int32_t)s[i].y;
-            if (p) p[i] = (int32_t)s[i].z;
-            if (k) k[i] = s[i].w;
+            if (r) r[i] = (int32_t)s[i * W];
+            if (c) c[i] = (int32_t)s[i * W + 1];
+            if (p) p[i] = (int32_t)s[i * W + 2];
+            if (k) k[i] = s[i * W + 3];
         }
     } catch (const std::exception& ex) {
         return fail(FI_ERR_OOM, std::string("env_read_state: ") + ex.what());

@@ -196,10 +196,10 @@ __device__ __forceinline__ uint4 philox4(uint64_t seed, uint64_t e, uint32_t str
 
 // counter streams of the generator: the synthetic batch's tensors (misc.hip), the actor's action
 // draws (actor.hip), the ring's replay draws (ring.hip), its prioritised draws (prio.hip), the
-// built-in environment's resets (env.hip)
+// built-in environments' resets (Catch: env.hip, Breakout: breakout.hip)
 enum {
     ST_OBS = 0, ST_MU = 1, ST_ACT = 2, ST_REW = 3, ST_DONE = 4, ST_FRAME = 5, ST_SAMPLE = 6, ST_REPLAY = 7,
-    ST_PRIO = 8, ST_ENV = 9
+    ST_PRIO = 8, ST_ENV = 9, ST_BREAKOUT = 10
 };
 
 }  // namespace fi

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""A learning measurement on an environment that needs the frame stack: the Atari policy on the
+built-in Breakout environment, everything on one device (include/fi_breakout.h, fi_env.h,
+fi_rollout.h, fi_train.h). N = B = 256 environments, T = 20, A = 3, max_steps = 1000.
+
+Each unroll: env.rollout(actor, T) -> learner.step_rollout(actor) -> actor.set_params(the learner's
+blob). `--unrolls` unrolls per configuration (default 2,000); every `--window` unrolls (default 100)
+the mean score of the episodes that finished in the window, from the differences of env.stats().
+Two configurations, each with its own learner, actor and environment of the same seeds:
+
+  adam      Adam at the repository's default rate, nothing else set
+  rmsprop   RMSProp with monobeast's numbers: lr 4.8e-4, decay 0.99, eps 0.01, momentum 0, the rate
+            annealed linearly to 0 over the run, rewards clipped to [-1, 1]
+
+and, as the baseline, the score of the untrained policy measured the same way over one window with a
+third learner's initial parameters and no learner step. An episode ends when the ball passes the
+paddle or after max_steps steps; its return is the number of bricks it cleared (a reward of 1 each).
+Nothing is tuned and there is no threshold: the curves are the result. Prints one JSON line and
+writes it to profiles/train_breakout.json.
+
+    python scripts/train_breakout.py [--out profiles/train_breakout.json] [--unrolls 2000] [--window 100]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from freeimpala_amd import breakout, build_info, hip  # noqa: E402
+from freeimpala_amd.actor import Actor  # noqa: E402
+from freeimpala_amd.learner import DeviceLearner  # noqa: E402
+
+N, T, A, GAMMA, SEED, MAX_STEPS = 256, 20, 3, 0.99, 1, 1000
+RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
+
+
+def make_learner(config: str, unrolls: int) -> DeviceLearner:
+    if config == "rmsprop":
+        L = DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", optimizer="rmsprop",
+                          lr=RMSPROP["lr"], seed=SEED)
+        L.set_rmsprop(RMSPROP["decay"], RMSPROP["momentum"], RMSPROP["eps"])
+        L.set_lr_schedule(0.0, unrolls)
+        L.set_reward_clip(RMSPROP["reward_clip"])
+        return L
+    return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
+
+
+def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
+    now = e.stats()
+    n, s = now["episodes"] - before["episodes"], now["return_sum"] - before["return_sum"]
+    return now, dict(episodes=n, mean_return=round(s / n, 4) if n else None)
+
+
+def train(config: str, unrolls: int, window: int) -> dict:
+    L = make_learner(config, unrolls)
+    a = Actor("atari", N, num_actions=A, seed=SEED)
+    blob, version = L.get_blob()
+    a.set_params(blob, version)
+    a.begin_rollout(T)
+    e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
+    assert e.rollout(a, 1) == 1  # step 0 of the first unroll
+    curve, seen, last = [], e.stats(), {}
+    t0 = time.perf_counter()
+    for u in range(1, unrolls + 1):
+        assert e.rollout(a, T) == T
+        last = L.step_rollout(a)
+        blob, version = L.get_blob()
+        a.set_params(blob, version)
+        if u % window == 0:
+            seen, w = window_of(e, seen)
+            curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
+    wall = time.perf_counter() - t0
+    state = L.train_state()
+    a.sync()
+    a.end_rollout()
+    for h in (a, e, L):
+        h.close()
+    return dict(curve=curve, wall_s=round(wall, 3), env_steps=unrolls * N * T, env_steps_per_s=round(unrolls * N * T / wall, 1),
+                learner_version=last.get("version"), train_state=state)
+
+
+def untrained(window: int) -> dict:
+    """One window of the loop with a never-stepped learner's parameters: no record, no learner step."""
+    L = make_learner("adam", 1)
+    a = Actor("atari", N, num_actions=A, seed=SEED)
+    blob, version = L.get_blob()
+    a.set_params(blob, version)
+    e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
+    assert e.rollout(a, 1) == 1
+    seen = e.stats()
+    for _ in range(window):
+        assert e.rollout(a, T) == T
+    a.sync()
+    _, w = window_of(e, seen)
+    for h in (a, e, L):
+        h.close()
+    return w
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_breakout.json"))
+    ap.add_argument("--unrolls", type=int, default=2000)
+    ap.add_argument("--window", type=int, default=100)
+    args = ap.parse_args()
+    if hip.device_count() < 1:
+        raise SystemExit("train_breakout: no HIP device; nothing is measured without one")
+    t0 = time.perf_counter()
+    base = untrained(args.window)
+    runs = {c: train(c, args.unrolls, args.window) for c in ("adam", "rmsprop")}
+    res = dict(what="learning measurement on an environment that needs the frame stack: the Atari policy on "
+                    "device-resident Breakout, mean score of the episodes finished in every window of unrolls; two "
+                    "documented settings, nothing tuned, no threshold",
+               num_envs=N, batch=N, seq_len=T, num_actions=A, gamma=GAMMA, seed=SEED, max_steps=MAX_STEPS,
+               unrolls=args.unrolls, window_unrolls=args.window, return_range=[0, MAX_STEPS],
+               configs=dict(adam="Adam, fi_learner_config_init's rate and moments, global-norm clip 40",
+                            rmsprop=dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)")),
+               untrained_policy=base, runs=runs, wall_s=round(time.perf_counter() - t0, 3),
+               source_hash=build_info.source_hash())
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
