@@ -111,6 +111,30 @@ class Actor:
         a = np.frombuffer(p, np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p)
         check(lib().fi_actor_set_params(self._h, a.ctypes.data, a.nbytes, version), "fi_actor_set_params")
 
+    # --- parameters from device memory, in stream order (include/fi_publish.h)
+    def set_params_dev(self, learner) -> None:
+        """The learner's newest publication (``learner.publish()``), enqueued on this handle's stream:
+        no host copy, no wait. ``version`` becomes the publication's tag. May be called on this
+        actor's thread while another thread drives the learner."""
+        from . import publish
+        check(publish.lib().fi_actor_set_params_dev(self._h, learner._h), "fi_actor_set_params_dev")
+
+    def set_params_ptr(self, params_ptr: int, count: int, version: int = 0, ready_event=None) -> int | None:
+        """``count`` fp32 parameters from device memory, behind ``ready_event``; returns the handle's
+        "params read" event, recorded behind the copy."""
+        from . import publish
+        ev = _P()
+        check(publish.lib().fi_actor_set_params_ptr(self._h, params_ptr, count, version, ready_event, C.byref(ev)),
+              "fi_actor_set_params_ptr")
+        return ev.value
+
+    def read_params(self) -> np.ndarray:
+        """Waits for the stream: the handle's fp32 parameters."""
+        from . import publish
+        out = np.empty(self.param_count, np.float32)
+        check(publish.lib().fi_actor_read_params(self._h, out.ctypes.data, out.size), "fi_actor_read_params")
+        return out
+
     @property
     def version(self) -> int:
         return int(lib().fi_actor_version(self._h))

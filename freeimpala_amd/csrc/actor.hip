@@ -26,6 +26,7 @@
 #include "fi_actor.h"
 #include "fi_common.h"
 #include "fi_env.h"
+#include "fi_publish.h"
 #include "fi_rollout.h"
 #include "kernels.h"
 #include "records.h"
@@ -236,6 +237,8 @@ struct fi_actor {
     hipEvent_t dev_done = nullptr;
     int* dev_bad = nullptr;
     bool dev_pending = false;
+    // parameters from device memory (fi_publish.h), made by the first such call: recorded behind the copy
+    hipEvent_t params_read = nullptr;
     // rollout recording (fi_rollout.h): two device buffers of N entries; buf[fill] takes the unroll
     // being acted, buf[ready] (or -1) holds a completed unroll until it is released
     struct {
@@ -284,6 +287,7 @@ static void destroy(fi_actor* a) {
     for (auto& e : a->ev)
         if (e) (void)hipEventDestroy(e);
     if (a->dev_done) (void)hipEventDestroy(a->dev_done);
+    if (a->params_read) (void)hipEventDestroy(a->params_read);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -432,6 +436,37 @@ extern "C" int fi_actor_set_params(fi_actor* a, const void* blob, size_t bytes, 
     } catch (const std::exception& e) {
         return fail(FI_ERR_OOM, std::string("actor_set_params: ") + e.what());
     }
+}
+
+// fi_publish.h: the same hand-over from device memory, in stream order, with no wait
+extern "C" int fi_actor_set_params_ptr(fi_actor* a, const float* params_dev, size_t count, uint64_t version,
+                                       void* ready_event, void** read_event_out) {
+    FI_REQUIRE(a, "actor_set_params_ptr: null actor");
+    if (read_event_out) *read_event_out = nullptr;
+    FI_REQUIRE(count == a->nparams, "actor_set_params_ptr: count " + std::to_string(count) +
+                                        " != the handle's parameter count " + std::to_string(a->nparams));
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_TRY(check_dev_span(a->dev, params_dev, count * sizeof(float), 16, "actor_set_params_ptr: params_dev"));
+    if (!a->params_read) FI_HIP_CHECK(hipEventCreateWithFlags(&a->params_read, hipEventDisableTiming));
+    if (ready_event) FI_HIP_CHECK(hipStreamWaitEvent(a->stream, (hipEvent_t)ready_event, 0));
+    FI_HIP_CHECK(hipMemcpyAsync(a->params, params_dev, count * sizeof(float), hipMemcpyDeviceToDevice, a->stream));
+    FI_HIP_CHECK(hipEventRecord(a->params_read, a->stream));  // behind the copy: the source is free again
+    if (a->atari) FI_TRY(atari_sync_weights(a->atari, a->params, a->stream));
+    a->version = version;
+    a->have_params = true;
+    if (read_event_out) *read_event_out = (void*)a->params_read;
+    return FI_OK;
+}
+
+extern "C" int fi_actor_read_params(fi_actor* a, float* dst, size_t count) {
+    FI_REQUIRE(a && dst, "actor_read_params: null argument");
+    FI_REQUIRE(count == a->nparams, "actor_read_params: count " + std::to_string(count) +
+                                        " != the handle's parameter count " + std::to_string(a->nparams));
+    if (!a->have_params) return fail(FI_ERR_STATE, "actor_read_params: no parameters yet");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    FI_HIP_CHECK(hipMemcpyAsync(dst, a->params, count * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+    FI_HIP_CHECK(hipStreamSynchronize(a->stream));
+    return FI_OK;
 }
 
 extern "C" int fi_actor_set_mode(fi_actor* a, int mode) {
@@ -913,7 +948,7 @@ extern "C" int fi_rollout_end(fi_actor* a) {
 // what fi_ring_push_rollout (ring.hip) compares with the ring, and fi_env_rollout (env.hip) with the environment
 int fi::actor_info(const fi_actor* a, ActorInfo* out) {
     FI_REQUIRE(a && out, "actor_info: null argument");
-    *out = ActorInfo{a->dev, a->N, a->cfg.arch, a->ro.T > 0, a->stream};
+    *out = ActorInfo{a->dev, a->N, a->cfg.arch, a->ro.T > 0, a->stream, a->A, a->D, a->H};
     return FI_OK;
 }
 

@@ -193,13 +193,31 @@ int learner_set_column_weights(fi_learner* l, const float* w_host, int32_t n, Sc
 int learner_clear_column_weights(fi_learner* l);
 int learner_column_weights(fi_learner* l, float* dst, int32_t n);
 
-// actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, and what fi_env_rollout
-// (env.hip) enqueues behind
+// learner.cpp: what publish.hip (fi_publish.h) reads of a learner, and where its publication block
+// hangs. learner.cpp names nothing of publish.hip: the block arrives with its free function, which
+// fi_learner_destroy calls behind the wait for the learner's streams.
+struct PublishView {
+    int dev, arch, A, D, H, dtype;
+    size_t nparams;
+    const float* params;
+    const int* skipped;  // the device word that counts updates skipped since the last check
+    hipStream_t stream;
+    uint64_t version;  // the count of enqueued updates
+    void* block;
+};
+int learner_publish_view(fi_learner* l, PublishView* out);
+// the block alone, an atomic load: the one thing of a learner another handle's thread may read
+void* learner_publish_block(const fi_learner* l);
+void learner_set_publish_block(fi_learner* l, void* block, void (*free_fn)(void*));
+
+// actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
+// (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner
 struct ActorInfo {
     int dev, N;
     int arch;
     bool recording;
     hipStream_t stream;
+    int A, D, H;
 };
 int actor_info(const fi_actor* a, ActorInfo* out);
 // actor.hip: `bytes` from p on are device memory of device `dev` inside one allocation, and p is

@@ -12,6 +12,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -115,6 +116,10 @@ struct fi_learner {
     uint64_t lr_steps = 0;
     bool lr_sched = false;
     float reward_clip = 0.f;  // 0: off
+    // the publication block (fi_publish.h): made and freed by publish.hip, which hands its free
+    // function in with it; atomic because an actor's thread may look it up (fi_actor_set_params_dev)
+    std::atomic<void*> publish{nullptr};
+    void (*publish_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -219,6 +224,7 @@ static void destroy(fi_learner* l) {
     if (!l) return;
     if (l->stream) hipStreamSynchronize(l->stream);
     if (l->copy_stream) hipStreamSynchronize(l->copy_stream);
+    if (void* pb = l->publish.load()) l->publish_free(pb);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -1284,6 +1290,21 @@ extern "C" int fi_learner_synth_batch(fi_learner* l, uint64_t seed, int32_t b_gl
                         l->act, l->rew, l->disc, l->frames, l->stream));
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
     return FI_OK;
+}
+
+// what publish.hip (fi_publish.h) reads of a learner; the block itself is publish.hip's
+int fi::learner_publish_view(fi_learner* l, PublishView* out) {
+    FI_REQUIRE(l && out, "learner_publish_view: null argument");
+    *out = PublishView{l->dev,    l->cfg.arch, l->A,      l->D,       l->H, l->cfg.publish_dtype, l->nparams,
+                       l->params, l->bad + 2,  l->stream, l->version, l->publish.load(std::memory_order_acquire)};
+    return FI_OK;
+}
+
+void* fi::learner_publish_block(const fi_learner* l) { return l ? l->publish.load(std::memory_order_acquire) : nullptr; }
+
+void fi::learner_set_publish_block(fi_learner* l, void* block, void (*free_fn)(void*)) {
+    l->publish_free = free_fn;
+    l->publish.store(block, std::memory_order_release);
 }
 
 // ------------------------------------------------------------------ params

@@ -263,6 +263,38 @@ class DeviceLearner:
         check(train.lib().fi_train_get_state(self._h, C.byref(st)), "fi_train_get_state")
         return st.as_dict()
 
+    # --- parameters published on the device (include/fi_publish.h)
+    def publish(self) -> int:
+        """Enqueue a publication of the parameters as they are at this point of the learner's stream
+        (the published form: ``publish.round_params``); nothing waits. Returns the tag: the count of
+        updates enqueued so far. ``actor.set_params_dev(learner)`` takes it."""
+        from . import publish
+        tag = C.c_uint64(0)
+        check(publish.lib().fi_publish_params(self._h, C.byref(tag)), "fi_publish_params")
+        return tag.value
+
+    def publish_state(self) -> dict:
+        """fi_publish_get_state as a dict: publications, slot, tag, version (exact: waits), dtype and
+        the readers recorded against each slot."""
+        from . import publish
+        st = publish.PublishState()
+        check(publish.lib().fi_publish_get_state(self._h, C.byref(st)), "fi_publish_get_state")
+        return st.as_dict()
+
+    def published(self) -> tuple[np.ndarray, int]:
+        """(the newest snapshot as fp32, its exact version); waits for the publication."""
+        from . import publish
+        out = np.empty(self.param_count, np.float32)
+        ver = C.c_uint64(0)
+        check(publish.lib().fi_publish_read(self._h, out.ctypes.data, out.size, C.byref(ver)), "fi_publish_read")
+        return out, ver.value
+
+    @property
+    def publish_event(self) -> int | None:
+        """The newest publication's hipEvent_t, None before the first."""
+        from . import publish
+        return publish.lib().fi_publish_event(self._h)
+
     def step_segments_dev(self, segments, stats: bool = True) -> dict:
         """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum
         to the batch; segment k fills the next n columns once its event (or None) has completed."""

@@ -17,6 +17,7 @@
 #include "fi_actor.h"
 #include "fi_env.h"
 #include "fi_gather.h"
+#include "fi_publish.h"
 #include "fi_rollout.h"
 
 namespace freeimpala_amd {
@@ -73,6 +74,15 @@ public:
     // the blob DeviceLearner::publish fills (fp32 or bf16) and its version
     bool load(const std::vector<char>& blob, uint64_t version) {
         return ok(fi_actor_set_params(h_, blob.data(), blob.size(), version));
+    }
+    // the learner's newest publication on the device (include/fi_publish.h: DeviceLearner::publish_dev),
+    // in stream order: nothing is copied through the host and nothing waits. May be called on this
+    // actor's thread while another thread drives the learner.
+    bool set_params_dev(fi_learner* learner) { return ok(fi_actor_set_params_dev(h_, learner)); }
+    // waits for the stream: the handle's fp32 parameters
+    bool read_params(std::vector<float>& out) {
+        out.resize(param_count());
+        return ok(fi_actor_read_params(h_, out.data(), out.size()));
     }
     bool set_greedy(bool greedy) { return ok(fi_actor_set_mode(h_, greedy ? FI_ACT_GREEDY : FI_ACT_SAMPLE)); }
     bool seed(uint64_t seed, uint64_t draw = 0) { return ok(fi_actor_seed(h_, seed, draw)); }

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "fi_learner.h"
+#include "fi_publish.h"
 #include "fi_train.h"
 
 namespace freeimpala_amd {
@@ -444,6 +445,14 @@ public:
         blob.resize(param_bytes());
         if (fi_learner_get_params(handles_[p], blob.data(), blob.size(), &version) != FI_OK)
             return fail(p, fi_last_error());
+        return true;
+    }
+    // The same parameters published on the device (include/fi_publish.h): enqueued on the learner's
+    // stream into a snapshot slot, nothing waits. An actor on the same device takes the newest one
+    // with DeviceActor::set_params_dev(handle(p)). tag: the count of updates enqueued so far.
+    bool publish_dev(size_t p, uint64_t& tag) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        if (fi_publish_params(handles_[p], &tag) != FI_OK) return fail(p, fi_last_error());
         return true;
     }
     // --starting-model resume (Model::loadFromDisk bytes + version).

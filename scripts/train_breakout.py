@@ -19,6 +19,17 @@ Nothing is tuned and there is no threshold: the curves are the result. Prints on
 writes it to profiles/train_breakout.json.
 
     python scripts/train_breakout.py [--out profiles/train_breakout.json] [--unrolls 2000] [--window 100]
+                                   [--publish host|device] [--overlap]
+
+`--publish device` replaces the blob round trip by learner.publish() -> actor.set_params_dev(learner)
+(include/fi_publish.h): the parameters stay on the device and neither side waits for the hand-over.
+`--overlap` (with `--publish device`) also enqueues the next unroll's acting before this unroll's
+step: env.rollout(actor, T - 1) -> learner.step_rollouts_async([actor]) -> learner.publish() ->
+actor.set_params_dev(learner) -> env.rollout(actor, 1). The last step of an unroll writes record 0 of
+the next one into the buffer the learner reads, so it goes behind the release; the T - 1 steps before
+it run while the learner steps, one version behind, which `batch_versions` reports and V-trace
+corrects. The host waits once per window (learner.wait()). The default is `host` without overlap:
+the loop above, unchanged. The other modes write profiles/train_breakout_device_publish.json.
 """
 from __future__ import annotations
 
@@ -56,11 +67,51 @@ def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
     return now, dict(episodes=n, mean_return=round(s / n, 4) if n else None)
 
 
-def train(config: str, unrolls: int, window: int) -> dict:
+def hand_over(L: DeviceLearner, a: Actor, publish: str) -> None:
+    if publish == "device":
+        L.publish()
+        a.set_params_dev(L)
+    else:
+        blob, version = L.get_blob()
+        a.set_params(blob, version)
+
+
+def train_overlapped(config: str, unrolls: int, window: int) -> dict:
+    """--publish device --overlap: unroll u + 1 is acted while unroll u is stepped; one host wait per window."""
     L = make_learner(config, unrolls)
     a = Actor("atari", N, num_actions=A, seed=SEED)
-    blob, version = L.get_blob()
-    a.set_params(blob, version)
+    hand_over(L, a, "device")
+    a.begin_rollout(T)
+    e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
+    assert e.rollout(a, T + 1) == T + 1  # the first unroll, complete
+    curve, seen, last = [], e.stats(), {}
+    t0 = time.perf_counter()
+    for u in range(1, unrolls + 1):
+        assert e.rollout(a, T - 1) == T - 1
+        L.step_rollouts_async([a])
+        hand_over(L, a, "device")
+        assert e.rollout(a, 1) == 1
+        if u % window == 0:
+            last = L.wait()
+            bv = L.batch_versions
+            seen, w = window_of(e, seen)
+            curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4),
+                              batch_versions=[bv["min"], bv["max"], round(bv["mean"], 3)], **w))
+    last = L.wait()
+    wall = time.perf_counter() - t0
+    state = L.train_state()
+    a.sync()
+    a.end_rollout()
+    for h in (a, e, L):
+        h.close()
+    return dict(curve=curve, wall_s=round(wall, 3), env_steps=unrolls * N * T, env_steps_per_s=round(unrolls * N * T / wall, 1),
+                learner_version=last.get("version"), train_state=state)
+
+
+def train(config: str, unrolls: int, window: int, publish: str = "host") -> dict:
+    L = make_learner(config, unrolls)
+    a = Actor("atari", N, num_actions=A, seed=SEED)
+    hand_over(L, a, publish)
     a.begin_rollout(T)
     e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
     assert e.rollout(a, 1) == 1  # step 0 of the first unroll
@@ -69,8 +120,7 @@ def train(config: str, unrolls: int, window: int) -> dict:
     for u in range(1, unrolls + 1):
         assert e.rollout(a, T) == T
         last = L.step_rollout(a)
-        blob, version = L.get_blob()
-        a.set_params(blob, version)
+        hand_over(L, a, publish)
         if u % window == 0:
             seen, w = window_of(e, seen)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
@@ -104,15 +154,25 @@ def untrained(window: int) -> dict:
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_breakout.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--unrolls", type=int, default=2000)
     ap.add_argument("--window", type=int, default=100)
+    ap.add_argument("--publish", choices=("host", "device"), default="host")
+    ap.add_argument("--overlap", action="store_true")
     args = ap.parse_args()
+    if args.overlap and args.publish != "device":
+        raise SystemExit("train_breakout: --overlap needs --publish device (the host blob waits for the learner)")
+    default_mode = args.publish == "host" and not args.overlap
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "train_breakout.json" if default_mode else "train_breakout_device_publish.json")
     if hip.device_count() < 1:
         raise SystemExit("train_breakout: no HIP device; nothing is measured without one")
     t0 = time.perf_counter()
     base = untrained(args.window)
-    runs = {c: train(c, args.unrolls, args.window) for c in ("adam", "rmsprop")}
+    if args.overlap:
+        runs = {c: train_overlapped(c, args.unrolls, args.window) for c in ("adam", "rmsprop")}
+    else:
+        runs = {c: train(c, args.unrolls, args.window, args.publish) for c in ("adam", "rmsprop")}
     res = dict(what="learning measurement on an environment that needs the frame stack: the Atari policy on "
                     "device-resident Breakout, mean score of the episodes finished in every window of unrolls; two "
                     "documented settings, nothing tuned, no threshold",
@@ -122,6 +182,8 @@ def main() -> None:
                             rmsprop=dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)")),
                untrained_policy=base, runs=runs, wall_s=round(time.perf_counter() - t0, 3),
                source_hash=build_info.source_hash())
+    if not default_mode:
+        res.update(publish=args.publish, overlap=args.overlap)
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
