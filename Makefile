@@ -7,9 +7,9 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
-HDRS := $(wildcard $(CSRC)/*.h) include/fi_learner.h include/fi_farmer.h include/fi_actor.h include/fi_rollout.h include/fi_gather.h include/fi_ring.h include/fi_prio.h include/fi_weights.h include/fi_env.h include/fi_train.h include/fi_breakout.h include/fi_publish.h
+HDRS := $(wildcard $(CSRC)/*.h) include/fi_learner.h include/fi_farmer.h include/fi_actor.h include/fi_rollout.h include/fi_gather.h include/fi_ring.h include/fi_prio.h include/fi_weights.h include/fi_env.h include/fi_train.h include/fi_breakout.h include/fi_publish.h include/fi_explore.h
 
 all: $(LIBDIR)/libfi_learner.so oracle host tools
 
@@ -82,6 +82,12 @@ build/host_train_check: tests/cpp/host_train_check.cpp include/freeimpala_amd/de
 # include/fi_publish.h: one unroll of device Catch, an asynchronous step, a publication and a hand-over on the device
 host: build/host_publish_check
 build/host_publish_check: tests/cpp/host_publish_check.cpp include/freeimpala_amd/device_learner.hpp include/freeimpala_amd/device_actor.hpp include/fi_publish.h include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
+	@mkdir -p build
+	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
+# include/fi_explore.h: a recording Atari actor with an epsilon ladder on device Catch, a learner steps from its unroll
+host: build/host_explore_check
+build/host_explore_check: tests/cpp/host_explore_check.cpp include/freeimpala_amd/device_learner.hpp include/freeimpala_amd/device_actor.hpp include/fi_explore.h include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
 	@mkdir -p build
 	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 

@@ -7,7 +7,9 @@ draws their actions on the device:
   a.set_params(blob, version)                 # the bytes of DeviceLearner.get_blob() / get_params()
   out = a.act_planes(planes, episode_start)   # dict(actions (N,), logits (N, A), values (N,))
 
-The logits returned are the policy's own: they are what an actor writes into a record's mu field.
+The logits returned are the policy's own: they are what an actor writes into a record's mu field,
+unless exploration is set (``set_exploration``, include/fi_explore.h): then the draw has a temperature
+and per-environment epsilons, the dicts gain ``behaviour_logits`` and those go into mu.
 An Atari handle keeps every environment's 4-frame stack on the device (``act_planes`` sends one
 84x84 plane per environment; ``stacks()`` reads them back); ``act_frames`` takes whole stacks.
 Everything runs in HIP kernels of libfi_learner.so; there is no CPU path."""
@@ -21,6 +23,7 @@ from . import _abi
 from ._abi import check
 
 FI_ACT_SAMPLE, FI_ACT_GREEDY = 0, 1
+FI_ERR_STATE, FI_ERR_NONFINITE = -4, -7  # include/fi_learner.h
 MODES = {"sample": FI_ACT_SAMPLE, "greedy": FI_ACT_GREEDY}
 PHASES = ["h2d", "push", "forward", "sample", "d2h"]
 PLANE_BYTES = 84 * 84
@@ -89,6 +92,7 @@ class Actor:
         self._h = _P()
         check(lib().fi_actor_create(C.byref(cfg), C.byref(self._h)), "fi_actor_create")
         self.arch, self.N, self.A, self.D, self.H = arch, num_envs, num_actions, obs_dim, hidden
+        self._explore_used = False  # set_exploration was called: act calls look for behaviour logits
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -158,11 +162,18 @@ class Actor:
 
     def _finish(self, rc, what, out):
         """A call that reports NaN / Inf rows has still filled its outputs: they ride on the error."""
+        err = None
         try:
-            check(rc, what)
+            check(rc, what)  # first: it reads fi_last_error(), which the probe below may overwrite
         except _abi.FiError as e:
-            e.outputs = out
-            raise
+            err = e
+        if rc in (_abi.FI_OK, FI_ERR_NONFINITE):
+            mu = self._behaviour()
+            if mu is not None:
+                out["behaviour_logits"] = mu
+        if err is not None:
+            err.outputs = out
+            raise err
         return out
 
     def act_obs(self, obs) -> dict:
@@ -266,9 +277,61 @@ class Actor:
         from . import hip
         self.sync()
         o = self.outputs_dev()
-        return dict(actions=hip.download_ptr(o["actions"], np.int32, (self.N,)),
-                    logits=hip.download_ptr(o["logits"], np.float32, (self.N, self.A)),
-                    values=hip.download_ptr(o["values"], np.float32, (self.N,)))
+        out = dict(actions=hip.download_ptr(o["actions"], np.int32, (self.N,)),
+                   logits=hip.download_ptr(o["logits"], np.float32, (self.N, self.A)),
+                   values=hip.download_ptr(o["values"], np.float32, (self.N,)))
+        mu = self._behaviour()
+        if mu is not None:
+            out["behaviour_logits"] = mu
+        return out
+
+    # --- exploration (include/fi_explore.h; the rule: freeimpala_amd/explore.py)
+    def set_exploration(self, temperature: float = 1.0, epsilon=None) -> None:
+        """Draw with a temperature and epsilon (None: 0, a scalar, or N values); the behaviour logits
+        go into the records' mu. Allowed between any two act calls. temperature 1 with every epsilon
+        0 is ``clear_exploration``. Greedy mode ignores both."""
+        from . import explore
+        eps = None
+        if epsilon is not None:
+            e = np.asarray(epsilon, np.float32)
+            if e.ndim > 0 and e.size != self.N:
+                raise ValueError(f"epsilon: {e.shape} is neither a scalar nor {self.N} values")
+            eps = np.ascontiguousarray(np.broadcast_to(e.reshape(-1) if e.ndim else e, (self.N,)))
+        check(explore.lib().fi_explore_set(self._h, temperature, eps.ctypes.data if eps is not None else None),
+              "fi_explore_set")
+        self._explore_used = True
+
+    def clear_exploration(self) -> None:
+        from . import explore
+        check(explore.lib().fi_explore_clear(self._h), "fi_explore_clear")
+
+    def exploration(self) -> dict:
+        """dict(temperature, epsilon (N,) fp32, active); inactive: temperature 1, epsilon 0."""
+        from . import explore
+        t, act = C.c_float(0), C.c_int(0)
+        eps = np.empty(self.N, np.float32)
+        check(explore.lib().fi_explore_get(self._h, C.byref(t), eps.ctypes.data, C.byref(act)), "fi_explore_get")
+        return dict(temperature=float(t.value), epsilon=eps, active=bool(act.value))
+
+    def behaviour_ptr(self) -> int:
+        """Device pointer of the last act call's behaviour logits float[N*A], behind
+        ``outputs_dev()["done_event"]``; FiError (rc = FI_ERR_STATE) unless that call explored."""
+        from . import explore
+        p = _P()
+        check(explore.lib().fi_explore_behaviour_dev(self._h, C.byref(p)), "fi_explore_behaviour_dev")
+        return p.value
+
+    def _behaviour(self):
+        """The last act call's behaviour logits (waits), or None when it drew by the plain rule."""
+        if not self._explore_used or not self.exploration()["active"]:  # fi_explore_get never fails
+            return None
+        from . import explore
+        mu = np.empty((self.N, self.A), np.float32)
+        rc = explore.lib().fi_explore_read_behaviour(self._h, mu.ctypes.data, mu.size)
+        if rc == FI_ERR_STATE:  # greedy mode, or set since the last act call
+            return None
+        check(rc, "fi_explore_read_behaviour")
+        return mu
 
     def outcome_dev(self, rewards_ptr: int, discounts_ptr: int, ready_event=None) -> None:
         """``outcome`` from N rewards and N discounts in device memory."""

@@ -12,6 +12,8 @@
 //     device memory, with the kernels of rollout.hip, and hands completed unrolls to a learner
 //   * the act call and the outcome on device pointers (fi_env.h) enqueue the same launches on the
 //     caller's memory, without the copies and without the wait
+//   * an exploring handle (fi_explore.h) draws with explore.hip's kernel instead, and records the
+//     behaviour logits that kernel writes in place of the policy's
 // One HIP stream per handle, no global mutable state, no HIP graphs.
 #include <hip/hip_runtime.h>
 
@@ -239,6 +241,9 @@ struct fi_actor {
     bool dev_pending = false;
     // parameters from device memory (fi_publish.h), made by the first such call: recorded behind the copy
     hipEvent_t params_read = nullptr;
+    // exploration (fi_explore.h): filled by explore.hip through actor_explore_state(), its launcher
+    // included, so that this file names nothing of explore.hip and links without it
+    ExploreState ex;
     // rollout recording (fi_rollout.h): two device buffers of N entries; buf[fill] takes the unroll
     // being acted, buf[ready] (or -1) holds a completed unroll until it is released
     struct {
@@ -288,6 +293,8 @@ static void destroy(fi_actor* a) {
         if (e) (void)hipEventDestroy(e);
     if (a->dev_done) (void)hipEventDestroy(a->dev_done);
     if (a->params_read) (void)hipEventDestroy(a->params_read);
+    if (a->ex.eps) (void)hipFree(a->ex.eps);
+    if (a->ex.mu) (void)hipFree(a->ex.mu);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -535,6 +542,19 @@ static int record_step(fi_actor* a, int kind, bool completing, const void* d_in,
     return FI_OK;
 }
 
+// The draw of one act call. *d_mu: what a record's mu field takes -- the policy's logits, or, while
+// exploration is active in sample mode (fi_explore.h), the behaviour logits the other kernel writes.
+static int sample(fi_actor* a, const float* d_log, int32_t* d_act, int* d_bad, const float** d_mu) {
+    a->ex.mu_valid = a->ex.active && a->mode == FI_ACT_SAMPLE;
+    if (!a->ex.mu_valid) {
+        *d_mu = d_log;
+        return sample_actions_launch(d_log, a->N, a->A, a->mode, a->seed, a->draw, d_act, d_bad, a->stream);
+    }
+    FI_REQUIRE(a->ex.launch && a->ex.eps && a->ex.mu, "act: exploration is active without its launcher and buffers");
+    *d_mu = a->ex.mu;
+    return a->ex.launch(d_log, a->N, a->A, a->ex.tau, a->ex.eps, a->seed, a->draw, d_act, a->ex.mu, d_bad, a->stream);
+}
+
 static void mark(fi_actor* a, int i) {
     if (a->profiling) (void)hipEventRecord(a->ev[i], a->stream);
 }
@@ -605,7 +625,8 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     else FI_TRY(atari_forward(a->atari, kind == IN_PLANES ? a->stacks : a->frames, d_log, d_val, a->stream));
     mark(a, PH_SAMPLE);
     FI_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), a->stream));
-    FI_TRY(sample_actions_launch(d_log, a->N, a->A, a->mode, a->seed, a->draw, d_act, d_bad, a->stream));
+    const float* d_mu = nullptr;
+    FI_TRY(sample(a, d_log, d_act, d_bad, &d_mu));
     mark(a, PH_D2H);
     FI_HIP_CHECK(hipMemcpyAsync(a->pin_out, a->out, a->out_bytes, hipMemcpyDeviceToHost, a->stream));
     mark(a, PH_COUNT);
@@ -616,7 +637,7 @@ static int act(fi_actor* a, int kind, const void* in, const uint8_t* start, int3
     // phases and the caller does not wait for them
     if (recording)
         FI_TRY(record_step(a, kind, completing, kind == IN_PLANES ? (const void*)a->planes : (const void*)a->obs,
-                           a->planes ? a->planes + N * kPlaneBytes : nullptr, d_log, d_act));
+                           a->planes ? a->planes + N * kPlaneBytes : nullptr, d_mu, d_act));
     if (a->profiling) {
         for (int p = 0; p < PH_COUNT; ++p) {
             float ms = 0.f;
@@ -702,9 +723,10 @@ static int act_dev(fi_actor* a, int kind, const void* in, const uint8_t* start, 
     if (kind == IN_OBS) FI_TRY(mlp_forward(a, (const float*)in, d_log, d_val));
     else FI_TRY(atari_forward(a->atari, a->stacks, d_log, d_val, a->stream));
     // dev_bad is not zeroed here: it adds up until fi_actor_sync reads it
-    FI_TRY(sample_actions_launch(d_log, a->N, a->A, a->mode, a->seed, a->draw, d_act, a->dev_bad, a->stream));
+    const float* d_mu = nullptr;
+    FI_TRY(sample(a, d_log, d_act, a->dev_bad, &d_mu));
     a->draw++;
-    if (a->ro.T > 0) FI_TRY(record_step(a, kind, completing, in, start, d_log, d_act));
+    if (a->ro.T > 0) FI_TRY(record_step(a, kind, completing, in, start, d_mu, d_act));
     FI_HIP_CHECK(hipEventRecord(a->dev_done, a->stream));
     return FI_OK;
 }
@@ -785,6 +807,10 @@ extern "C" int fi_actor_phase_times(fi_actor* a, float* ms, int n, int* n_calls)
     a->phase_calls = 0;
     return FI_OK;
 }
+
+// ------------------------------------------------------------------ exploration (fi_explore.h)
+// the handle's exploration state, for explore.hip, which owns the C entry points and the kernel
+ExploreState* fi::actor_explore_state(fi_actor* a) { return a ? &a->ex : nullptr; }
 
 // ------------------------------------------------------------------ standalone kernels
 extern "C" int fi_push_planes(uint8_t* stacks_dev, const uint8_t* planes_dev, const uint8_t* episode_start_dev, int N,

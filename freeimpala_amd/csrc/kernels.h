@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "fi_gather.h"
 #include "fi_learner.h"
@@ -224,5 +225,25 @@ int actor_info(const fi_actor* a, ActorInfo* out);
 // `align`-byte aligned: the check of fi_learner_step_entries_dev for the pointers of fi_env.h.
 // FI_ERR_INVALID with `what` (call: argument) in the message
 int check_dev_span(int dev, const void* p, size_t bytes, size_t align, const std::string& what);
+
+// Exploration (include/fi_explore.h). explore.hip owns the kernel and the C entry points; an actor
+// handle (actor.hip) carries this state and, while `active` in sample mode, calls `launch` where it
+// launches the plain sampler and records `mu` in place of the policy's logits. actor.hip names
+// nothing of explore.hip -- the launcher arrives with fi_explore_set -- so a library without
+// explore.hip links. eps (N floats) and mu (N * A) are device memory made by the first
+// fi_explore_set and freed with the handle; eps_host mirrors eps; mu_valid: the last act call ran
+// `launch` and mu holds its rows. eps == nullptr in a launch: all 0.
+typedef int (*BehaviourLaunchFn)(const float* logits, int N, int A, float tau, const float* eps, uint64_t seed,
+                                 uint64_t draw, int32_t* actions, float* mu, int* nonfinite, hipStream_t s);
+struct ExploreState {
+    bool active = false;
+    float tau = 1.f;
+    std::vector<float> eps_host;
+    float* eps = nullptr;
+    float* mu = nullptr;
+    bool mu_valid = false;
+    BehaviourLaunchFn launch = nullptr;
+};
+ExploreState* actor_explore_state(fi_actor* a);  // actor.hip; nullptr for a null handle
 
 }  // namespace fi

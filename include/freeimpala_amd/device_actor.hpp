@@ -16,6 +16,7 @@
 
 #include "fi_actor.h"
 #include "fi_env.h"
+#include "fi_explore.h"
 #include "fi_gather.h"
 #include "fi_publish.h"
 #include "fi_rollout.h"
@@ -86,6 +87,21 @@ public:
     }
     bool set_greedy(bool greedy) { return ok(fi_actor_set_mode(h_, greedy ? FI_ACT_GREEDY : FI_ACT_SAMPLE)); }
     bool seed(uint64_t seed, uint64_t draw = 0) { return ok(fi_actor_seed(h_, seed, draw)); }
+
+    // Exploration (include/fi_explore.h): the draw gets a temperature and one epsilon per environment
+    // (empty: all 0), and a recording handle writes the behaviour logits into its records' mu. Allowed
+    // between any two act calls; greedy mode ignores both.
+    bool set_exploration(float temperature, const std::vector<float>& epsilon = {}) {
+        if (!epsilon.empty() && epsilon.size() != (size_t)cfg_.num_envs)
+            return bad("set_exploration: epsilon must be empty or hold num_envs floats");
+        return ok(fi_explore_set(h_, temperature, epsilon.empty() ? nullptr : epsilon.data()));
+    }
+    bool clear_exploration() { return ok(fi_explore_clear(h_)); }
+    // the last act call's behaviour logits (N * A; waits): false unless that call explored
+    bool read_behaviour(std::vector<float>& out) {
+        out.resize((size_t)cfg_.num_envs * cfg_.num_actions);
+        return ok(fi_explore_read_behaviour(h_, out.data(), out.size()));
+    }
 
     // obs: N * obs_dim floats (MLP)
     bool act_obs(const std::vector<float>& obs, ActResult& out) {

@@ -20,6 +20,7 @@ writes it to profiles/train_breakout.json.
 
     python scripts/train_breakout.py [--out profiles/train_breakout.json] [--unrolls 2000] [--window 100]
                                    [--publish host|device] [--overlap]
+                                   [--temperature TAU] [--epsilon EPS] [--epsilon-alpha ALPHA]
 
 `--publish device` replaces the blob round trip by learner.publish() -> actor.set_params_dev(learner)
 (include/fi_publish.h): the parameters stay on the device and neither side waits for the hand-over.
@@ -30,6 +31,13 @@ the next one into the buffer the learner reads, so it goes behind the release; t
 it run while the learner steps, one version behind, which `batch_versions` reports and V-trace
 corrects. The host waits once per window (learner.wait()). The default is `host` without overlap:
 the loop above, unchanged. The other modes write profiles/train_breakout_device_publish.json.
+
+`--temperature`, `--epsilon` and `--epsilon-alpha` make the training actors explore (include/fi_explore.h):
+a sampling temperature, an epsilon for every environment, and with `--epsilon-alpha` Ape-X's ladder
+across the N environments, eps_i = EPS ** (1 + ALPHA i / (N - 1)). The records' mu are then the behaviour
+logits, so V-trace stays right; the scores are those of the exploring actors. The untrained baseline
+stays the plain draw. The defaults (1, 0, no ladder) leave the loop and the output unchanged; anything
+else writes profiles/train_breakout_explore.json.
 """
 from __future__ import annotations
 
@@ -76,11 +84,19 @@ def hand_over(L: DeviceLearner, a: Actor, publish: str) -> None:
         a.set_params(blob, version)
 
 
-def train_overlapped(config: str, unrolls: int, window: int) -> dict:
+def explore(a: Actor, ex: dict | None) -> None:
+    if ex:
+        from freeimpala_amd.explore import epsilon_ladder
+        eps = ex["epsilon"] if ex["epsilon_alpha"] is None else epsilon_ladder(N, ex["epsilon"], ex["epsilon_alpha"])
+        a.set_exploration(ex["temperature"], eps)
+
+
+def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = None) -> dict:
     """--publish device --overlap: unroll u + 1 is acted while unroll u is stepped; one host wait per window."""
     L = make_learner(config, unrolls)
     a = Actor("atari", N, num_actions=A, seed=SEED)
     hand_over(L, a, "device")
+    explore(a, ex)
     a.begin_rollout(T)
     e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
     assert e.rollout(a, T + 1) == T + 1  # the first unroll, complete
@@ -108,10 +124,11 @@ def train_overlapped(config: str, unrolls: int, window: int) -> dict:
                 learner_version=last.get("version"), train_state=state)
 
 
-def train(config: str, unrolls: int, window: int, publish: str = "host") -> dict:
+def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dict | None = None) -> dict:
     L = make_learner(config, unrolls)
     a = Actor("atari", N, num_actions=A, seed=SEED)
     hand_over(L, a, publish)
+    explore(a, ex)
     a.begin_rollout(T)
     e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
     assert e.rollout(a, 1) == 1  # step 0 of the first unroll
@@ -159,10 +176,20 @@ def main() -> None:
     ap.add_argument("--window", type=int, default=100)
     ap.add_argument("--publish", choices=("host", "device"), default="host")
     ap.add_argument("--overlap", action="store_true")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--epsilon", type=float, default=0.0)
+    ap.add_argument("--epsilon-alpha", type=float, default=None)
     args = ap.parse_args()
     if args.overlap and args.publish != "device":
         raise SystemExit("train_breakout: --overlap needs --publish device (the host blob waits for the learner)")
     default_mode = args.publish == "host" and not args.overlap
+    ex = None
+    if args.temperature != 1.0 or args.epsilon != 0.0:
+        ex = dict(temperature=args.temperature, epsilon=args.epsilon, epsilon_alpha=args.epsilon_alpha)
+    elif args.epsilon_alpha is not None:
+        raise SystemExit("train_breakout: --epsilon-alpha is the ladder's exponent and needs --epsilon, its base")
+    if args.out is None and ex:
+        args.out = os.path.join(ROOT, "profiles", "train_breakout_explore.json")
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "train_breakout.json" if default_mode else "train_breakout_device_publish.json")
     if hip.device_count() < 1:
@@ -170,9 +197,9 @@ def main() -> None:
     t0 = time.perf_counter()
     base = untrained(args.window)
     if args.overlap:
-        runs = {c: train_overlapped(c, args.unrolls, args.window) for c in ("adam", "rmsprop")}
+        runs = {c: train_overlapped(c, args.unrolls, args.window, ex) for c in ("adam", "rmsprop")}
     else:
-        runs = {c: train(c, args.unrolls, args.window, args.publish) for c in ("adam", "rmsprop")}
+        runs = {c: train(c, args.unrolls, args.window, args.publish, ex) for c in ("adam", "rmsprop")}
     res = dict(what="learning measurement on an environment that needs the frame stack: the Atari policy on "
                     "device-resident Breakout, mean score of the episodes finished in every window of unrolls; two "
                     "documented settings, nothing tuned, no threshold",
@@ -184,6 +211,9 @@ def main() -> None:
                source_hash=build_info.source_hash())
     if not default_mode:
         res.update(publish=args.publish, overlap=args.overlap)
+    if ex:
+        res.update(exploration=dict(ex, note="the training actors explore and record their behaviour logits as mu; "
+                                             "the scores are the exploring actors' own; the untrained baseline is the plain draw"))
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
