@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wal
             -munsafe-fp-atomics
 SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
-HDRS := $(wildcard $(CSRC)/*.h) include/fi_learner.h include/fi_farmer.h include/fi_actor.h include/fi_rollout.h include/fi_gather.h include/fi_ring.h include/fi_prio.h include/fi_weights.h include/fi_env.h include/fi_train.h include/fi_breakout.h include/fi_publish.h include/fi_explore.h
+HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/fi_*.h)
 
 all: $(LIBDIR)/libfi_learner.so oracle host tools
 
@@ -28,68 +28,21 @@ $(LIBDIR)/libfi_learner.so: $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-# C++ host-side check program (include/freeimpala_amd/device_learner.hpp over the C ABI)
-host: build/host_learner_check build/replay_check
+# C++ host-side check programs, one per header of the C ABI and its C++ wrapper (tests/cpp/host_<name>_check.cpp):
+# learner (device_learner.hpp), actor, rollout, rollouts (fi_gather.h), ring, env, breakout, train, publish, explore
+HOST_CHECKS := learner actor rollout rollouts ring env breakout train publish explore
+HOST_CXX = g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+host: $(HOST_CHECKS:%=build/host_%_check) build/replay_check build/host_util_check
+build/host_%_check: tests/cpp/host_%_check.cpp $(wildcard include/*.h include/freeimpala_amd/*.hpp) $(LIBDIR)/libfi_learner.so
+	@mkdir -p build
+	$(HOST_CXX)
 build/replay_check: tests/cpp/replay_check.cpp $(wildcard include/freeimpala_amd/*.hpp) include/fi_learner.h $(LIBDIR)/libfi_learner.so
 	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-build/host_learner_check: tests/cpp/host_learner_check.cpp include/freeimpala_amd/device_learner.hpp include/fi_learner.h $(LIBDIR)/libfi_learner.so
+	$(HOST_CXX)
+# the internal host helpers (csrc/host_util.h) on their own: HIP flags, because the header pulls in device helpers
+build/host_util_check: tests/cpp/host_util_check.cpp $(HDRS) $(LIBDIR)/libfi_learner.so
 	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/freeimpala_amd/device_actor.hpp over include/fi_actor.h: an MLP and an Atari actor fed a learner's blob
-host: build/host_actor_check
-build/host_actor_check: tests/cpp/host_actor_check.cpp include/freeimpala_amd/device_actor.hpp include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_rollout.h: an MLP and an Atari actor record one unroll each on the device and a learner steps from it
-host: build/host_rollout_check
-build/host_rollout_check: tests/cpp/host_rollout_check.cpp include/freeimpala_amd/device_actor.hpp include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_gather.h: two MLP and two Atari actors of different sizes fill one learner batch each
-host: build/host_rollouts_check
-build/host_rollouts_check: tests/cpp/host_rollouts_check.cpp include/freeimpala_amd/device_actor.hpp include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_ring.h: an MLP and an Atari actor push two unrolls each into a device entry ring, a learner steps FIFO and mixed
-host: build/host_ring_check
-build/host_ring_check: tests/cpp/host_ring_check.cpp include/freeimpala_amd/device_ring.hpp include/freeimpala_amd/device_actor.hpp include/fi_ring.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_env.h: a recording Atari actor driven by the built-in device environment, a learner steps from its unrolls
-host: build/host_env_check
-build/host_env_check: tests/cpp/host_env_check.cpp include/freeimpala_amd/device_actor.hpp include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_breakout.h: a recording Atari actor driven by the device Breakout environment, a learner steps from two unrolls
-host: build/host_breakout_check
-build/host_breakout_check: tests/cpp/host_breakout_check.cpp include/freeimpala_amd/device_breakout.hpp include/freeimpala_amd/device_actor.hpp include/fi_breakout.h include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_train.h through LearnerConfig's flags: RMSProp, a schedule and a reward clip; save, load, the same bytes
-host: build/host_train_check
-build/host_train_check: tests/cpp/host_train_check.cpp include/freeimpala_amd/device_learner.hpp include/fi_train.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_publish.h: one unroll of device Catch, an asynchronous step, a publication and a hand-over on the device
-host: build/host_publish_check
-build/host_publish_check: tests/cpp/host_publish_check.cpp include/freeimpala_amd/device_learner.hpp include/freeimpala_amd/device_actor.hpp include/fi_publish.h include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
-
-# include/fi_explore.h: a recording Atari actor with an epsilon ladder on device Catch, a learner steps from its unroll
-host: build/host_explore_check
-build/host_explore_check: tests/cpp/host_explore_check.cpp include/freeimpala_amd/device_learner.hpp include/freeimpala_amd/device_actor.hpp include/fi_explore.h include/fi_env.h include/fi_gather.h include/fi_rollout.h include/fi_actor.h include/fi_learner.h $(LIBDIR)/libfi_learner.so
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+	$(HIPCC) $(HIPFLAGS) -x hip $< -o $@ -L$(LIBDIR) -lfi_learner '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 # the cmd/freeimpala-shaped binary on freeimpala_amd::Learner (include/freeimpala_amd/learner.hpp)
 tools: build/fi_freeimpala build/fi_freeimpala_mpi

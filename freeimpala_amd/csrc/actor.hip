@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -30,6 +31,7 @@
 #include "fi_env.h"
 #include "fi_publish.h"
 #include "fi_rollout.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "records.h"
 
@@ -262,11 +264,7 @@ struct fi_actor {
 };
 
 static int dalloc(fi_actor* a, void** p, size_t bytes) {
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(FI_ERR_OOM, std::string("actor: hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    }
+    FI_TRY(dev_alloc(p, std::max<size_t>(bytes, 16), "actor"));
     a->allocs.push_back(*p);
     return FI_OK;
 }
@@ -328,18 +326,11 @@ static int create(const fi_actor_config* cfg, fi_actor** out) {
         FI_REQUIRE(cfg->num_actions >= 2 && cfg->num_actions <= 18,
                    "actor_create: the Atari policy needs 2 <= A <= 18 (the full ALE action set is 18)");
     }
-    int ndev = 0;
-    FI_HIP_CHECK(hipGetDeviceCount(&ndev));
-    FI_REQUIRE(cfg->device >= 0 && cfg->device < ndev, "actor_create: no such HIP device");
-    FI_HIP_CHECK(hipSetDevice(cfg->device));
+    FI_TRY(use_device(cfg->device, "actor_create"));
 
     fi_actor* a = new (std::nothrow) fi_actor();
     FI_REQUIRE(a, "actor_create: out of host memory");
-    struct Guard {
-        fi_actor* a;
-        bool ok = false;
-        ~Guard() { if (!ok) destroy(a); }
-    } guard{a};
+    std::unique_ptr<fi_actor, void (*)(fi_actor*)> guard(a, destroy);
     a->cfg = *cfg;
     a->dev = cfg->device;
     a->N = cfg->num_envs;
@@ -387,17 +378,12 @@ static int create(const fi_actor_config* cfg, fi_actor** out) {
         }
     }
     FI_HIP_CHECK(hipStreamSynchronize(a->stream));
-    guard.ok = true;
-    *out = a;
+    *out = guard.release();
     return FI_OK;
 }
 
 extern "C" int fi_actor_create(const fi_actor_config* cfg, fi_actor** out) {
-    try {
-        return create(cfg, out);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("actor_create: ") + e.what());
-    }
+    return guarded("actor_create", FI_ERR_OOM, [&] { return create(cfg, out); });
 }
 
 extern "C" void fi_actor_destroy(fi_actor* a) {
@@ -438,11 +424,7 @@ static int set_params(fi_actor* a, const void* src, size_t bytes, uint64_t versi
 }
 
 extern "C" int fi_actor_set_params(fi_actor* a, const void* blob, size_t bytes, uint64_t version) {
-    try {
-        return set_params(a, blob, bytes, version);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("actor_set_params: ") + e.what());
-    }
+    return guarded("actor_set_params", FI_ERR_OOM, [&] { return set_params(a, blob, bytes, version); });
 }
 
 // fi_publish.h: the same hand-over from device memory, in stream order, with no wait
@@ -670,26 +652,6 @@ extern "C" int fi_actor_act_planes(fi_actor* a, const uint8_t* planes, const uin
 }
 
 // ------------------------------------------------------------------ the act call on device pointers (fi_env.h)
-int fi::check_dev_span(int dev, const void* p, size_t bytes, size_t align, const std::string& what) {
-    FI_REQUIRE(p, what + " is null");
-    FI_REQUIRE((uintptr_t)p % align == 0, what + " must be " + std::to_string(align) + "-byte aligned");
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != dev) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, what + " is not device memory of the handle's device " + std::to_string(dev));
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, what + " lies in no device allocation");
-    }
-    const size_t have = size - (size_t)((const char*)p - (const char*)base);
-    FI_REQUIRE(bytes <= have, what + ": the allocation ends " + std::to_string(have) + " bytes behind the pointer, " +
-                                  std::to_string(bytes) + " are read");
-    return FI_OK;
-}
-
 // the event and the counter of the device calls, made by the first of them
 static int ensure_dev_calls(fi_actor* a) {
     if (!a->dev_done) FI_HIP_CHECK(hipEventCreateWithFlags(&a->dev_done, hipEventDisableTiming));
@@ -836,24 +798,16 @@ static int rollout_begin(fi_actor* a, int32_t T) {
     ro.rec = atari ? (size_t)kPlaneRecBytes : (size_t)kMlpRecBytes;
     ro.entry = (size_t)(T + 1) * ro.rec + (atari ? (size_t)kHistoryBytes : 0);
     const size_t bytes = (size_t)a->N * ro.entry;
-    struct Guard {
-        fi_actor* a;
-        bool ok = false;
-        ~Guard() { if (!ok) rollout_free(a); }
-    } guard{a};
+    std::unique_ptr<fi_actor, void (*)(fi_actor*)> guard(a, rollout_free);
     for (int i = 0; i < 2; ++i) {
-        const hipError_t e = hipMalloc((void**)&ro.buf[i], bytes);
-        if (e != hipSuccess) {
-            ro.buf[i] = nullptr;
-            (void)hipGetLastError();
-            return fail(FI_ERR_OOM, "rollout_begin: hipMalloc(" + std::to_string(bytes) + ") for rollout buffer " +
-                                        std::to_string(i) + " of 2: " + hipGetErrorString(e));
-        }
+        FI_TRY(dev_alloc((void**)&ro.buf[i], bytes, "rollout_begin: rollout buffer " + std::to_string(i) + " of 2"));
         FI_HIP_CHECK(hipMemsetAsync(ro.buf[i], 0, bytes, a->stream));
         FI_HIP_CHECK(hipEventCreateWithFlags(&ro.ready_ev[i], hipEventDisableTiming));
     }
     const size_t ob = 2 * (size_t)a->N * sizeof(float);
-    if (hipMalloc((void**)&ro.outcome, ob) != hipSuccess || hipHostMalloc((void**)&ro.pin_outcome, ob, hipHostMallocDefault) != hipSuccess) {
+    FI_TRY(dev_alloc((void**)&ro.outcome, ob, "rollout_begin: the outcome staging"));
+    if (hipHostMalloc((void**)&ro.pin_outcome, ob, hipHostMallocDefault) != hipSuccess) {
+        ro.pin_outcome = nullptr;
         (void)hipGetLastError();
         return fail(FI_ERR_OOM, "rollout_begin: the outcome staging (" + std::to_string(ob) + " bytes) cannot be allocated");
     }
@@ -864,16 +818,12 @@ static int rollout_begin(fi_actor* a, int32_t T) {
     ro.ready = -1;
     ro.need_outcome = false;
     ro.last_buf = -1;
-    guard.ok = true;
+    guard.release();
     return FI_OK;
 }
 
 extern "C" int fi_rollout_begin(fi_actor* a, int32_t seq_len) {
-    try {
-        return rollout_begin(a, seq_len);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("rollout_begin: ") + e.what());
-    }
+    return guarded("rollout_begin", FI_ERR_OOM, [&] { return rollout_begin(a, seq_len); });
 }
 
 extern "C" int fi_rollout_outcome(fi_actor* a, const float* rewards, const float* discounts) {
@@ -978,38 +928,42 @@ int fi::actor_info(const fi_actor* a, ActorInfo* out) {
     return FI_OK;
 }
 
+// What a step from an actor's unroll refuses of the actor (`who`: the call and the subject, "the
+// actor" or "actor k"): it records, and its device, policy and unroll length are the learner's;
+// whole_batch: its environments are the learner's batch.
+static int actor_fits(const fi_actor* a, const LearnerInfo& li, const std::string& who, bool whole_batch) {
+    if (a->ro.T == 0) return fail(FI_ERR_STATE, who + " does not record (fi_rollout_begin)");
+    auto differs = [&](const char* what, int actor, int learner) {
+        return fail(FI_ERR_INVALID, who + "'s " + what + " " + std::to_string(actor) + " != the learner's " +
+                                        std::to_string(learner));
+    };
+    if (a->dev != li.dev) return differs("device", a->dev, li.dev);
+    if (a->cfg.arch != li.arch) return differs("arch", a->cfg.arch, li.arch);
+    if (a->A != li.A) return differs("num_actions", a->A, li.A);
+    if (li.arch == FI_ARCH_MLP && a->D != li.D) return differs("obs_dim", a->D, li.D);
+    if (whole_batch && a->N != li.B) return differs("num_envs", a->N, li.B);
+    if (a->ro.T != li.T) return differs("rollout seq_len", a->ro.T, li.T);
+    return FI_OK;
+}
+
 // acquire, step, release. It lives here, not in learner.cpp, because it holds both handles: the
 // learner is driven through its C ABI, and learner.cpp stays free of the actor.
 extern "C" int fi_learner_step_rollout(fi_learner* l, fi_actor* a, fi_step_stats* out) {
     FI_REQUIRE(l && a, "step_rollout: null argument");
     LearnerInfo li{};
     FI_TRY(learner_info(l, &li));
-    if (a->ro.T == 0) return fail(FI_ERR_STATE, "step_rollout: the actor does not record (fi_rollout_begin)");
-    auto differs = [&](const char* what, int actor, int learner) {
-        return fail(FI_ERR_INVALID, std::string("step_rollout: the actor's ") + what + " " + std::to_string(actor) +
-                                        " != the learner's " + std::to_string(learner));
-    };
-    if (a->dev != li.dev) return differs("device", a->dev, li.dev);
-    if (a->cfg.arch != li.arch) return differs("arch", a->cfg.arch, li.arch);
-    if (a->A != li.A) return differs("num_actions", a->A, li.A);
-    if (li.arch == FI_ARCH_MLP && a->D != li.D) return differs("obs_dim", a->D, li.D);
-    if (a->N != li.B) return differs("num_envs", a->N, li.B);  // the learner's batch
-    if (a->ro.T != li.T) return differs("rollout seq_len", a->ro.T, li.T);
-    FI_REQUIRE(li.dev_entries_ok, "step_rollout: an Atari handle reads device entries in the planes format only "
-                                  "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    FI_TRY(actor_fits(a, li, "step_rollout: the actor", true));
+    FI_TRY(require_dev_entries(li.dev_entries_ok, "step_rollout"));
     const void* entries = nullptr;
     size_t stride = 0;
     void* ready = nullptr;
     FI_TRY(fi_rollout_acquire(a, &entries, &stride, &ready));
     const int rc = fi_learner_step_entries_dev(l, entries, stride, ready, out);
-    // FI_ERR_INVALID / FI_ERR_STATE / FI_ERR_HIP / FI_ERR_OOM: refused or broken before or at the enqueue,
-    // the unroll stays. Otherwise the step ran (and was waited for), whatever it then reported
-    // (FI_ERR_NONFINITE: update skipped): the ingest has read the buffer, and it goes back.
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
-    std::string why;
-    if (rc != FI_OK) why = fi_last_error();
-    FI_TRY(fi_rollout_release(a, fi_learner_entries_consumed_event(l)));
-    return rc == FI_OK ? FI_OK : fail(rc, why);
+    // Any other status: refused or broken before or at the enqueue, the unroll stays. Otherwise the
+    // step ran (and was waited for), whatever it then reported: the ingest has read the buffer, and
+    // it goes back.
+    if (!step_taken(rc)) return rc;
+    return finish_taken(rc, [&] { return fi_rollout_release(a, fi_learner_entries_consumed_event(l)); });
 }
 
 // ------------------------------------------------------------------ several actors, one batch (fi_gather.h)
@@ -1029,22 +983,12 @@ static int step_rollouts(fi_learner* l, fi_actor* const* actors, int32_t n, fi_s
         const std::string ak = nm + ": actor " + std::to_string(k);
         FI_REQUIRE(a, ak + " is null");
         for (int j = 0; j < k; ++j) FI_REQUIRE(actors[j] != a, ak + " is actor " + std::to_string(j) + " again");
-        if (a->ro.T == 0) return fail(FI_ERR_STATE, ak + " does not record (fi_rollout_begin)");
-        auto differs = [&](const char* what, int actor, int learner) {
-            return fail(FI_ERR_INVALID, ak + "'s " + what + " " + std::to_string(actor) + " != the learner's " +
-                                            std::to_string(learner));
-        };
-        if (a->dev != li.dev) return differs("device", a->dev, li.dev);
-        if (a->cfg.arch != li.arch) return differs("arch", a->cfg.arch, li.arch);
-        if (a->A != li.A) return differs("num_actions", a->A, li.A);
-        if (li.arch == FI_ARCH_MLP && a->D != li.D) return differs("obs_dim", a->D, li.D);
-        if (a->ro.T != li.T) return differs("rollout seq_len", a->ro.T, li.T);
+        FI_TRY(actor_fits(a, li, ak, false));
         envs += a->N;
     }
     FI_REQUIRE(envs == li.B, nm + ": the actors' num_envs sum to " + std::to_string(envs) + " != the learner's batch " +
                                  std::to_string(li.B));
-    FI_REQUIRE(li.dev_entries_ok, nm + ": an Atari handle reads device entries in the planes format only "
-                                       "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    FI_TRY(require_dev_entries(li.dev_entries_ok, nm));
     for (int k = 0; k < n; ++k)
         if (actors[k]->ro.ready < 0)
             return fail(FI_ERR_STATE, nm + ": actor " + std::to_string(k) + " has no completed unroll (record " +
@@ -1056,14 +1000,13 @@ static int step_rollouts(fi_learner* l, fi_actor* const* actors, int32_t n, fi_s
         FI_TRY(fi_rollout_acquire(actors[k], &segs[k].entries_dev, &segs[k].entry_stride, &segs[k].ready_event));
     }
     const int rc = wait ? fi_learner_step_segments_dev(l, segs, n, out) : fi_learner_step_segments_dev_async(l, segs, n);
-    // as fi_learner_step_rollout: the unrolls go back when the step ran (FI_ERR_NONFINITE: it ran and
-    // skipped its update) or, asynchronously, was enqueued -- the consumed event is recorded behind
-    // the ingest either way; after any other status they all stay
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
-    std::string why;
-    if (rc != FI_OK) why = fi_last_error();
-    for (int k = 0; k < n; ++k) FI_TRY(fi_rollout_release(actors[k], fi_learner_entries_consumed_event(l)));
-    return rc == FI_OK ? FI_OK : fail(rc, why);
+    // as fi_learner_step_rollout; asynchronously the unrolls go back when the step was enqueued -- the
+    // consumed event is recorded behind the ingest either way; after any other status they all stay
+    if (!step_taken(rc)) return rc;
+    return finish_taken(rc, [&]() -> int {
+        for (int k = 0; k < n; ++k) FI_TRY(fi_rollout_release(actors[k], fi_learner_entries_consumed_event(l)));
+        return FI_OK;
+    });
 }
 
 extern "C" int fi_learner_step_rollouts(fi_learner* l, fi_actor* const* actors, int32_t n_actors, fi_step_stats* out) {

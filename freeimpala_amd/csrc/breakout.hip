@@ -15,6 +15,7 @@
 #include "env_handle.h"
 #include "fi_breakout.h"
 #include "fi_common.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "records.h"
 
@@ -251,7 +252,7 @@ extern "C" int fi_breakout_read_state(fi_env* e, int32_t* r, int32_t* c, int32_t
     FI_TRY(require_breakout(e, "breakout_read_state"));
     FI_HIP_CHECK(hipSetDevice(e->dev));
     FI_HIP_CHECK(hipEventSynchronize(e->stepped));
-    try {
+    return guarded("breakout_read_state", FI_ERR_OOM, [&]() -> int {
         std::vector<uint32_t> s((size_t)e->N * kStateWords);
         FI_HIP_CHECK(hipMemcpy(s.data(), e->state, s.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (int i = 0; i < e->N; ++i) {
@@ -266,10 +267,8 @@ extern "C" int fi_breakout_read_state(fi_env* e, int32_t* r, int32_t* c, int32_t
             if (score) score[i] = (int32_t)(w[5] >> 16);
             if (bricks) bricks[i] = (uint64_t)w[6] | ((uint64_t)w[7] << 32);
         }
-    } catch (const std::exception& ex) {
-        return fail(FI_ERR_OOM, std::string("breakout_read_state: ") + ex.what());
-    }
-    return FI_OK;
+        return FI_OK;
+    });
 }
 
 extern "C" int fi_breakout_set_state(fi_env* e, const int32_t* r, const int32_t* c, const int32_t* p, const uint32_t* k,
@@ -298,7 +297,7 @@ extern "C" int fi_breakout_set_state(fi_env* e, const int32_t* r, const int32_t*
     }
     FI_HIP_CHECK(hipSetDevice(e->dev));
     FI_HIP_CHECK(hipEventSynchronize(e->stepped));
-    try {
+    FI_TRY(guarded("breakout_set_state", FI_ERR_OOM, [&]() -> int {
         std::vector<uint32_t> s((size_t)N * kStateWords);
         for (int i = 0; i < N; ++i) {
             uint32_t* w = s.data() + (size_t)i * kStateWords;
@@ -312,9 +311,8 @@ extern "C" int fi_breakout_set_state(fi_env* e, const int32_t* r, const int32_t*
             w[7] = (uint32_t)(bricks[i] >> 32);
         }
         FI_HIP_CHECK(hipMemcpy(e->state, s.data(), s.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    } catch (const std::exception& ex) {
-        return fail(FI_ERR_OOM, std::string("breakout_set_state: ") + ex.what());
-    }
+        return FI_OK;
+    }));
     FI_TRY(breakout_render_launch(e->state, e->planes, N, nullptr));
     FI_HIP_CHECK(hipEventRecord(e->stepped, nullptr));
     FI_HIP_CHECK(hipStreamSynchronize(nullptr));

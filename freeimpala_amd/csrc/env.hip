@@ -12,6 +12,7 @@
 // store; the two totals are 64-bit integer atomic adds, one pair per wave.
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "env_handle.h"
 #include "fi_common.h"
 #include "fi_env.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "records.h"
 
@@ -182,17 +184,10 @@ static int create(int kind, int32_t device, int32_t num_envs, float gamma, uint6
     *out = nullptr;
     FI_REQUIRE(num_envs >= 1 && num_envs <= 0x7fffffff / kPlanePieces, nm + ": 1 <= num_envs <= 4869582");
     FI_REQUIRE(gamma >= 0.f && gamma <= 1.f, nm + ": gamma outside [0, 1]");
-    int ndev = 0;
-    FI_HIP_CHECK(hipGetDeviceCount(&ndev));
-    FI_REQUIRE(device >= 0 && device < ndev, nm + ": no such HIP device");
-    FI_HIP_CHECK(hipSetDevice(device));
+    FI_TRY(use_device(device, nm));
     fi_env* e = new (std::nothrow) fi_env();
     FI_REQUIRE(e, nm + ": out of host memory");
-    struct Guard {
-        fi_env* e;
-        bool ok = false;
-        ~Guard() { if (!ok) destroy(e); }
-    } guard{e};
+    std::unique_ptr<fi_env, void (*)(fi_env*)> guard(e, destroy);
     e->dev = device;
     e->N = num_envs;
     e->gamma = gamma;
@@ -204,12 +199,7 @@ static int create(int kind, int32_t device, int32_t num_envs, float gamma, uint6
     const size_t o_planes = round_up(N * (size_t)e->state_words * 4), o_start = o_planes + round_up(N * kPlaneBytes),
                  o_rew = o_start + round_up(N), o_disc = o_rew + round_up(N * sizeof(float)),
                  o_tot = o_disc + round_up(N * sizeof(float)), bytes = o_tot + kAlign;
-    const hipError_t err = hipMalloc((void**)&e->block, bytes);
-    if (err != hipSuccess) {
-        e->block = nullptr;
-        (void)hipGetLastError();
-        return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(err));
-    }
+    FI_TRY(dev_alloc((void**)&e->block, bytes, nm));
     e->state = (uint4*)e->block;
     e->planes = (uint8_t*)(e->block + o_planes);
     e->start = (uint8_t*)(e->block + o_start);
@@ -222,18 +212,13 @@ static int create(int kind, int32_t device, int32_t num_envs, float gamma, uint6
     FI_TRY(render_launch(e, nullptr));
     FI_HIP_CHECK(hipEventRecord(e->stepped, nullptr));
     FI_HIP_CHECK(hipStreamSynchronize(nullptr));
-    guard.ok = true;
-    *out = e;
+    *out = guard.release();
     return FI_OK;
 }
 
 int fi::env_create_handle(int kind, int32_t device, int32_t num_envs, float gamma, uint64_t seed, int32_t max_steps,
                           const char* nm, fi_env** out) {
-    try {
-        return create(kind, device, num_envs, gamma, seed, max_steps, nm, out);
-    } catch (const std::exception& ex) {
-        return fail(FI_ERR_OOM, std::string(nm) + ": " + ex.what());
-    }
+    return guarded(nm, FI_ERR_OOM, [&] { return create(kind, device, num_envs, gamma, seed, max_steps, nm, out); });
 }
 
 extern "C" int fi_env_create(int32_t device, int32_t num_envs, float gamma, uint64_t seed, fi_env** out) {
@@ -284,7 +269,7 @@ extern "C" int fi_env_read_state(fi_env* e, int32_t* r, int32_t* c, int32_t* p, 
     FI_REQUIRE(e, "env_read_state: null environment");
     FI_HIP_CHECK(hipSetDevice(e->dev));
     FI_HIP_CHECK(hipEventSynchronize(e->stepped));
-    try {
+    return guarded("env_read_state", FI_ERR_OOM, [&]() -> int {
         const size_t W = (size_t)e->state_words;  // words 0-3 are r, c, p, k in every kind
         std::vector<uint32_t> s((size_t)e->N * W);
         FI_HIP_CHECK(hipMemcpy(s.data(), e->state, s.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -294,10 +279,8 @@ extern "C" int fi_env_read_state(fi_env* e, int32_t* r, int32_t* c, int32_t* p, 
             if (p) p[i] = (int32_t)s[i * W + 2];
             if (k) k[i] = s[i * W + 3];
         }
-    } catch (const std::exception& ex) {
-        return fail(FI_ERR_OOM, std::string("env_read_state: ") + ex.what());
-    }
-    return FI_OK;
+        return FI_OK;
+    });
 }
 
 extern "C" int fi_env_stats(fi_env* e, uint64_t* episodes, int64_t* return_sum) {

@@ -17,6 +17,7 @@
 
 #include "fi_common.h"
 #include "fi_explore.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace fi {
@@ -185,12 +186,7 @@ static int explore_set(fi_actor* a, float tau, const float* eps_host) {
     for (float** p : {&ex.eps, &ex.mu}) {
         if (*p) continue;
         const size_t bytes = (p == &ex.eps ? N : N * (size_t)ai.A) * sizeof(float);
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) {
-            *p = nullptr;
-            (void)hipGetLastError();
-            return fail(FI_ERR_OOM, "explore_set: hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-        }
+        FI_TRY(dev_alloc((void**)p, bytes, "explore_set"));
     }
     // in stream order behind every act call enqueued so far: their kernels read the old epsilons
     FI_HIP_CHECK(hipMemcpyAsync(ex.eps, next.data(), N * sizeof(float), hipMemcpyHostToDevice, ai.stream));
@@ -203,11 +199,7 @@ static int explore_set(fi_actor* a, float tau, const float* eps_host) {
 }
 
 extern "C" int fi_explore_set(fi_actor* a, float temperature, const float* epsilon_host) {
-    try {
-        return explore_set(a, temperature, epsilon_host);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("explore_set: ") + e.what());
-    }
+    return guarded("explore_set", FI_ERR_OOM, [&] { return explore_set(a, temperature, epsilon_host); });
 }
 
 extern "C" int fi_explore_clear(fi_actor* a) {

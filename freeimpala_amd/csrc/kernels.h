@@ -221,10 +221,7 @@ struct ActorInfo {
     int A, D, H;
 };
 int actor_info(const fi_actor* a, ActorInfo* out);
-// actor.hip: `bytes` from p on are device memory of device `dev` inside one allocation, and p is
-// `align`-byte aligned: the check of fi_learner_step_entries_dev for the pointers of fi_env.h.
-// FI_ERR_INVALID with `what` (call: argument) in the message
-int check_dev_span(int dev, const void* p, size_t bytes, size_t align, const std::string& what);
+// (the check of a caller's device pointers, check_dev_span, is host_util.h's)
 
 // Exploration (include/fi_explore.h). explore.hip owns the kernel and the C entry points; an actor
 // handle (actor.hip) carries this state and, while `active` in sample mode, calls `launch` where it

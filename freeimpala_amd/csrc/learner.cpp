@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -27,6 +28,7 @@
 #include "fi_common.h"
 #include "fi_rollout.h"
 #include "fi_train.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace fi {
@@ -149,13 +151,7 @@ struct fi_learner {
 static constexpr int kSqParts = 512;
 
 static int dalloc(fi_learner* l, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(FI_ERR_OOM, std::string("hipMalloc(") + std::to_string(bytes) + "): " +
-                                    hipGetErrorString(e));
-    }
+    FI_TRY(dev_alloc(p, bytes ? bytes : 16, "learner"));
     l->allocs.push_back(*p);
     return FI_OK;
 }
@@ -265,19 +261,12 @@ static int create(const fi_learner_config* cfg, fi_learner** out) {
     if (cfg->arch == FI_ARCH_MLP)
         FI_REQUIRE(cfg->obs_dim >= 1 && cfg->obs_dim <= 128 && cfg->hidden >= 1 && cfg->hidden <= 4096,
                    "create: MLP needs 1 <= obs_dim <= 128 (record schema), hidden <= 4096");
-    int ndev = 0;
-    FI_HIP_CHECK(hipGetDeviceCount(&ndev));
-    FI_REQUIRE(cfg->device >= 0 && cfg->device < ndev, "create: no such HIP device");
-    FI_HIP_CHECK(hipSetDevice(cfg->device));
+    FI_TRY(use_device(cfg->device, "create"));
 
     fi_learner* l = new (std::nothrow) fi_learner();
     FI_REQUIRE(l, "create: out of host memory");
     *out = nullptr;
-    struct Guard {
-        fi_learner* l;
-        bool ok = false;
-        ~Guard() { if (!ok) destroy(l); }
-    } guard{l};
+    std::unique_ptr<fi_learner, void (*)(fi_learner*)> guard(l, destroy);
 
     l->cfg = *cfg;
     l->opt_kind = cfg->optimizer;
@@ -358,17 +347,12 @@ static int create(const fi_learner_config* cfg, fi_learner** out) {
     FI_HIP_CHECK(hipMemsetAsync(l->disc, 0, TB * sizeof(float), l->stream));
     if (l->atari) FI_TRY(atari_sync_weights(l->atari, l->params, l->stream));
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
-    guard.ok = true;
-    *out = l;
+    *out = guard.release();
     return FI_OK;
 }
 
 extern "C" int fi_learner_create(const fi_learner_config* cfg, fi_learner** out) {
-    try {
-        return create(cfg, out);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("create: ") + e.what());
-    }
+    return guarded("create", FI_ERR_OOM, [&] { return create(cfg, out); });
 }
 
 extern "C" size_t fi_learner_param_count(const fi_learner* l) { return l ? l->nparams : 0; }
@@ -756,11 +740,7 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
 extern "C" int fi_learner_step_resident(fi_learner* l, fi_step_stats* out) {
     FI_REQUIRE(l, "step: null learner");
     FI_HIP_CHECK(hipSetDevice(l->dev));
-    try {
-        return run_step(l, nullptr, out);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("step: ") + e.what());
-    }
+    return guarded("step", FI_ERR_STATE, [&] { return run_step(l, nullptr, out); });
 }
 
 static void parallel_copy(char* dst, const void* const* entries, size_t n, size_t entry_bytes,
@@ -926,58 +906,48 @@ static int step_staged_slot(fi_learner* l, fi_step_stats* out, bool wait) {
 
 extern "C" int fi_learner_step(fi_learner* l, const void* const* entries, size_t n_entries,
                                size_t entry_bytes, fi_step_stats* out) {
-    try {
+    return guarded("step", FI_ERR_STATE, [&]() -> int {
         FI_TRY(stage_entries(l, entries, n_entries, entry_bytes));
         return step_staged_slot(l, out, true);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("step: ") + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_step_async(fi_learner* l, const void* const* entries, size_t n_entries,
                                      size_t entry_bytes) {
-    try {
+    return guarded("step_async", FI_ERR_STATE, [&]() -> int {
         FI_TRY(stage_entries(l, entries, n_entries, entry_bytes));
         return step_staged_slot(l, nullptr, false);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("step_async: ") + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_acquire_staging(fi_learner* l, void** dst, size_t* entry_stride) {
     FI_REQUIRE(l && dst, "acquire_staging: null argument");
-    try {
+    return guarded("acquire_staging", FI_ERR_STATE, [&]() -> int {
         FI_HIP_CHECK(hipSetDevice(l->dev));
         int s = 0;
         FI_TRY(acquire_slot(l, &s));
         *dst = l->pinned2[s];
         if (entry_stride) *entry_stride = l->rec_entry_bytes;
         return FI_OK;
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("acquire_staging: ") + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_step_staged(fi_learner* l, fi_step_stats* out) {
     FI_REQUIRE(l, "step_staged: null learner");
-    try {
+    return guarded("step_staged", FI_ERR_STATE, [&]() -> int {
         FI_HIP_CHECK(hipSetDevice(l->dev));
         FI_TRY(submit_slot(l));
         return step_staged_slot(l, out, true);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("step_staged: ") + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_step_staged_async(fi_learner* l) {
     FI_REQUIRE(l, "step_staged_async: null learner");
-    try {
+    return guarded("step_staged_async", FI_ERR_STATE, [&]() -> int {
         FI_HIP_CHECK(hipSetDevice(l->dev));
         FI_TRY(submit_slot(l));
         return step_staged_slot(l, nullptr, false);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string("step_staged_async: ") + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_wait(fi_learner* l, fi_step_stats* out) {
@@ -992,42 +962,16 @@ extern "C" int fi_learner_wait(fi_learner* l, fi_step_stats* out) {
 }
 
 // ------------------------------------------------------------------ entries in device memory (fi_rollout.h)
-// n entries, `stride` apart, from `entries` on: the stride covers an entry, both are 16-byte aligned, and the
-// whole span is device memory of the handle's device inside one allocation
+// the span check of host_util.h with the handle's own entry size, on the handle's device
 static int check_entry_span(fi_learner* l, const void* entries, size_t stride, int n, const std::string& nm) {
     const size_t need = entry_bytes_min(l);
-    FI_REQUIRE(stride >= need, nm + ": entry_stride " + std::to_string(stride) + " < " + std::to_string(need) +
-                                   " = fi_learner_entry_bytes()");
-    FI_REQUIRE(stride % 16 == 0 && (uintptr_t)entries % 16 == 0,
-               nm + ": entries_dev and entry_stride must be 16-byte aligned");
     FI_HIP_CHECK(hipSetDevice(l->dev));
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, entries) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != l->dev) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, nm + ": entries_dev is not device memory of the handle's device " +
-                                        std::to_string(l->dev));
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)entries) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, nm + ": entries_dev lies in no device allocation");
-    }
-    const size_t span = (size_t)(n - 1) * stride + need;
-    const size_t have = size - (size_t)((const char*)entries - (const char*)base);
-    FI_REQUIRE(span <= have, nm + ": the allocation ends " + std::to_string(have) + " bytes behind entries_dev, " +
-                                 std::to_string(n) + " entries need " + std::to_string(span));
-    return FI_OK;
+    return fi::check_entry_span(l->dev, entries, stride, n, need, nm, std::to_string(need) + " = fi_learner_entry_bytes()");
 }
 
 // an Atari handle reads device entries in the planes format only (the stacked one is a host format)
 static bool dev_entries_ok(const fi_learner* l) {
     return l->cfg.arch != FI_ARCH_ATARI || l->rec_format == FI_RECORDS_PLANES;
-}
-static int require_dev_entries(const fi_learner* l, const std::string& nm) {
-    FI_REQUIRE(dev_entries_ok(l), nm + ": an Atari handle reads device entries in the planes format only "
-                                       "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
-    return FI_OK;
 }
 
 // entries_consumed, created by the first step from device entries
@@ -1038,18 +982,16 @@ static int ensure_entries_consumed(fi_learner* l) {
 
 static int step_entries_dev(fi_learner* l, const void* entries, size_t stride, void* ready, fi_step_stats* out,
                             bool wait, const char* who) {
-    try {
+    return guarded(who, FI_ERR_STATE, [&]() -> int {
         const std::string nm = who;
         FI_REQUIRE(l && entries, nm + ": null argument");
-        FI_TRY(require_dev_entries(l, nm));
+        FI_TRY(require_dev_entries(dev_entries_ok(l), nm));
         FI_TRY(check_entry_span(l, entries, stride, l->B, nm));
         FI_TRY(ensure_entries_consumed(l));
         const hipEvent_t ev = (hipEvent_t)ready;
         const Entries e{entries, stride, l->rec_format};
         return finish_step(l, BatchSource{&ev, 1, ingest_entries, &e, l->entries_consumed, false, nullptr, nullptr}, out, wait);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_step_entries_dev(fi_learner* l, const void* entries_dev, size_t entry_stride,
@@ -1086,10 +1028,10 @@ static int step_gathered(fi_learner* l, const hipEvent_t* ready, int n_ready, In
 
 int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32_t n_segs, fi_step_stats* out,
                               bool wait, const char* who, IngestFn ingest) {
-    try {
+    return guarded(who, FI_ERR_STATE, [&]() -> int {
         const std::string nm = who;
         FI_REQUIRE(l && segs && ingest, nm + ": null argument");
-        FI_TRY(require_dev_entries(l, nm));
+        FI_TRY(require_dev_entries(dev_entries_ok(l), nm));
         FI_REQUIRE(n_segs >= 1 && n_segs <= FI_MAX_SEGMENTS,
                    nm + ": " + std::to_string(n_segs) + " segments, 1 .. " + std::to_string(FI_MAX_SEGMENTS) + " are taken");
         SegTable tab{};
@@ -1111,21 +1053,17 @@ int fi::learner_step_segments(fi_learner* l, const fi_entry_segment* segs, int32
         FI_REQUIRE(cols == l->B, nm + ": the segments hold " + std::to_string(cols) + " entries, the learner's batch is " +
                                      std::to_string(l->B));
         return step_gathered(l, ready, n_segs, ingest, &tab, out, wait);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
-    }
+    });
 }
 
 int fi::learner_step_columns(fi_learner* l, hipEvent_t ready, IngestFn ingest, const void* ctx, fi_step_stats* out,
                              bool wait, const char* who, const float* weights, ScaleFn scale) {
-    try {
+    return guarded(who, FI_ERR_STATE, [&]() -> int {
         const std::string nm = who;
         FI_REQUIRE(l && ingest, nm + ": null argument");
-        FI_TRY(require_dev_entries(l, nm));
+        FI_TRY(require_dev_entries(dev_entries_ok(l), nm));
         return step_gathered(l, &ready, 1, ingest, ctx, out, wait, weights, scale);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_STATE, std::string(who) + ": " + e.what());
-    }
+    });
 }
 
 extern "C" int fi_learner_batch_versions(fi_learner* l, fi_batch_versions* out) {

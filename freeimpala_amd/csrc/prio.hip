@@ -22,6 +22,7 @@
 #include "fi_common.h"
 #include "fi_prio.h"
 #include "fi_weights.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "ring_handle.h"
 
@@ -338,13 +339,12 @@ extern "C" int fi_prio_enable(fi_ring* r, float eta, float init_priority) {
     const size_t bytes = 4 * (size_t)r->C, ws = 8 * (size_t)kMaxChunks;
     uint32_t* table = nullptr;
     uint64_t* sums = nullptr;
-    hipError_t e = hipMalloc((void**)&table, bytes);
-    if (e == hipSuccess && (e = hipMalloc((void**)&sums, ws)) != hipSuccess) (void)hipFree(table);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_OOM, "prio_enable: hipMalloc(" + std::to_string(bytes) + " + " + std::to_string(ws) +
-                                    ") for the priorities of " + std::to_string(r->C) + " slots: " + hipGetErrorString(e));
+    FI_TRY(dev_alloc((void**)&table, bytes, "prio_enable: the priorities of " + std::to_string(r->C) + " slots"));
+    if (dev_alloc((void**)&sums, ws, "prio_enable: the chunk sums") != FI_OK) {
+        (void)hipFree(table);
+        return FI_ERR_OOM;
     }
+    hipError_t e = hipSuccess;
     hipEvent_t done = nullptr;
     if ((e = hipEventCreateWithFlags(&done, hipEventDisableTiming)) != hipSuccess ||
         (e = hipMemsetAsync(table, 0, bytes, r->stream)) != hipSuccess ||
@@ -445,37 +445,18 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
                nm + ": vs / values do not have the shapes (T, B) / (T + 1, B)");
     FI_TRY(ring_step_entries(r, li.B, nm));
     if (r->prio_q_cap < li.B) {
-        if (r->prio_q) {
-            FI_HIP_CHECK(hipEventSynchronize(r->prio_done));  // behind the last refresh, which read it
-            (void)hipFree(r->prio_q);
-            r->prio_q = nullptr;
-            r->prio_q_cap = 0;
-        }
-        const hipError_t e = hipMalloc((void**)&r->prio_q, 4 * (size_t)li.B);
-        if (e != hipSuccess) {
-            r->prio_q = nullptr;
-            (void)hipGetLastError();
-            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(4 * (size_t)li.B) + ") for the column priorities");
-        }
-        r->prio_q_cap = li.B;
+        // behind the last refresh, which read it
+        if (r->prio_q) FI_HIP_CHECK(hipEventSynchronize(r->prio_done));
+        FI_TRY(dev_grow(&r->prio_q, &r->prio_q_cap, li.B, nm + ": the column priorities"));
     }
     // importance weights: with beta == 0 or no replayed column nothing is computed or launched
     const bool weighted = r->beta > 0.f && n_fresh < li.B;
     if (weighted && r->is_w_cap < li.B) {
         if (r->is_w) {
             FI_HIP_CHECK(hipEventSynchronize(r->prio_done));  // behind the last step that read it
-            (void)hipFree(r->is_w);
-            r->is_w = nullptr;
-            r->is_w_cap = 0;
             r->is_w_valid = false;
         }
-        const hipError_t e = hipMalloc((void**)&r->is_w, 4 * (size_t)li.B);
-        if (e != hipSuccess) {
-            r->is_w = nullptr;
-            (void)hipGetLastError();
-            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(4 * (size_t)li.B) + ") for the importance weights");
-        }
-        r->is_w_cap = li.B;
+        FI_TRY(dev_grow(&r->is_w, &r->is_w_cap, li.B, nm + ": the importance weights"));
     }
     pb.beta = r->beta;
     pb.is_w = weighted ? r->is_w : nullptr;
@@ -490,24 +471,23 @@ static int step_prio(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
                                         pb.is_w, scale_columns_launch);
     // after any other status the counters stay and nothing is refreshed; a fill that was enqueued
     // wrote q_init to entries at or above prio_hi only, which read as q_init anyway
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) {
+    if (!step_taken(rc)) {
         if (weighted) r->is_w_valid = false;  // the weights buffer may have been rewritten
         return rc;
     }
     r->is_w_valid = weighted;
-    std::string why;
-    if (rc != FI_OK) why = fi_last_error();  // the launchers below leave it alone unless they fail
     if (filled > r->prio_hi) r->prio_hi = filled;
     r->prio_owner = l;
-    // the refresh, behind the step on the learner's stream: r->last was written by the draw in front
-    // of it on the same stream
-    hipStream_t s = (hipStream_t)fi_learner_stream(l);
-    FI_TRY(prio_from_td_launch((const float*)vs, (const float*)values, li.T, li.B, r->eta, r->prio_q, s, r->alpha));
-    FI_TRY(prio_scatter_launch(r->prio, r->C, r->last, r->prio_q, li.B, s));
-    FI_HIP_CHECK(hipEventRecord(r->prio_done, s));
-    r->have_prio_done = true;
-    if (rc != FI_OK) fail(rc, why);  // the step's message, for ring_step_taken to hand on
-    return ring_step_taken(l, r, n_fresh, li.B, rc);
+    return finish_taken(rc, [&]() -> int {
+        // the refresh, behind the step on the learner's stream: r->last was written by the draw in
+        // front of it on the same stream
+        hipStream_t s = (hipStream_t)fi_learner_stream(l);
+        FI_TRY(prio_from_td_launch((const float*)vs, (const float*)values, li.T, li.B, r->eta, r->prio_q, s, r->alpha));
+        FI_TRY(prio_scatter_launch(r->prio, r->C, r->last, r->prio_q, li.B, s));
+        FI_HIP_CHECK(hipEventRecord(r->prio_done, s));
+        r->have_prio_done = true;
+        return ring_step_taken(l, r, n_fresh, li.B);
+    });
 }
 
 extern "C" int fi_learner_step_ring_prioritized(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out) {

@@ -18,6 +18,7 @@
 
 #include "fi_common.h"
 #include "fi_publish.h"
+#include "host_util.h"
 #include "kernels.h"
 
 namespace fi {
@@ -129,13 +130,10 @@ int block_create(const PublishView& v, PublishBlock** out) {
     b->nparams = v.nparams;
     const size_t bytes = kHeaderBytes + v.nparams * sizeof(float);
     for (int s = 0; s < 2; ++s) {
-        const hipError_t e = hipMalloc((void**)&b->slot[s], bytes);
-        if (e != hipSuccess) {
-            b->slot[s] = nullptr;
-            (void)hipGetLastError();
+        const int rc = dev_alloc((void**)&b->slot[s], bytes, "publish_params: snapshot slot " + std::to_string(s) + " of 2");
+        if (rc != FI_OK) {
             block_free(b);
-            return fail(FI_ERR_OOM, "publish_params: hipMalloc(" + std::to_string(bytes) + ") for snapshot slot " +
-                                        std::to_string(s) + " of 2: " + hipGetErrorString(e));
+            return rc;
         }
         if (hipEventCreateWithFlags(&b->ready[s], hipEventDisableTiming) != hipSuccess) {
             b->ready[s] = nullptr;

@@ -10,10 +10,12 @@
 // space, ordinary vector stores, no LDS, no atomics.
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
 
 #include "fi_common.h"
 #include "fi_ring.h"
+#include "host_util.h"
 #include "ingest_kernels.h"
 #include "kernels.h"
 #include "ring_handle.h"
@@ -156,39 +158,24 @@ static int create(int32_t device, size_t entry_bytes, int64_t capacity, uint64_t
     FI_REQUIRE(device >= 0 && device < ndev, "ring_create: device " + std::to_string(device) + " of " + std::to_string(ndev));
     FI_HIP_CHECK(hipSetDevice(device));
     fi_ring* r = new fi_ring();
-    struct Guard {
-        fi_ring* r;
-        bool ok = false;
-        ~Guard() { if (!ok) destroy(r); }
-    } g{r};
+    std::unique_ptr<fi_ring, void (*)(fi_ring*)> guard(r, destroy);
     r->dev = device;
     r->entry = entry_bytes;
     r->C = capacity;
     r->seed = seed;
     const size_t bytes = (size_t)capacity * entry_bytes;
     FI_REQUIRE(bytes / entry_bytes == (size_t)capacity, "ring_create: capacity * entry_bytes passes 2^64");
-    const hipError_t e = hipMalloc((void**)&r->base, bytes);
-    if (e != hipSuccess) {
-        r->base = nullptr;
-        (void)hipGetLastError();
-        return fail(FI_ERR_OOM, "ring_create: hipMalloc(" + std::to_string(bytes) + ") for " + std::to_string(capacity) +
-                                    " slots: " + hipGetErrorString(e));
-    }
+    FI_TRY(dev_alloc((void**)&r->base, bytes, "ring_create: " + std::to_string(capacity) + " slots"));
     FI_HIP_CHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
     FI_HIP_CHECK(hipEventCreateWithFlags(&r->pushed, hipEventDisableTiming));
     FI_HIP_CHECK(hipMemsetAsync(r->base, 0, bytes, r->stream));
     FI_HIP_CHECK(hipStreamSynchronize(r->stream));
-    g.ok = true;
-    *out = r;
+    *out = guard.release();
     return FI_OK;
 }
 
 extern "C" int fi_ring_create(int32_t device, size_t entry_bytes, int64_t capacity, uint64_t seed, fi_ring** out) {
-    try {
-        return create(device, entry_bytes, capacity, seed, out);
-    } catch (const std::exception& e) {
-        return fail(FI_ERR_OOM, std::string("ring_create: ") + e.what());
-    }
+    return guarded("ring_create", FI_ERR_OOM, [&] { return create(device, entry_bytes, capacity, seed, out); });
 }
 
 extern "C" void fi_ring_destroy(fi_ring* r) { destroy(r); }
@@ -207,37 +194,13 @@ extern "C" int fi_ring_seed(fi_ring* r, uint64_t seed, uint64_t draw) {
 }
 
 // ------------------------------------------------------------------ push
-// the checks fi_learner_step_entries_dev makes on its buffer (learner.cpp: check_entry_span)
-static int check_source(const fi_ring* r, const void* entries, size_t stride, int n, const std::string& nm) {
-    FI_REQUIRE(stride >= r->entry, nm + ": entry_stride " + std::to_string(stride) + " < entry_bytes " +
-                                       std::to_string(r->entry));
-    FI_REQUIRE(stride % 16 == 0 && (uintptr_t)entries % 16 == 0,
-               nm + ": entries_dev and entry_stride must be 16-byte aligned");
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, entries) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != r->dev) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, nm + ": entries_dev is not device memory of the ring's device " +
-                                        std::to_string(r->dev));
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)entries) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FI_ERR_INVALID, nm + ": entries_dev lies in no device allocation");
-    }
-    const size_t span = (size_t)(n - 1) * stride + r->entry;
-    const size_t have = size - (size_t)((const char*)entries - (const char*)base);
-    FI_REQUIRE(span <= have, nm + ": the allocation ends " + std::to_string(have) + " bytes behind entries_dev, " +
-                                 std::to_string(n) + " entries need " + std::to_string(span));
-    return FI_OK;
-}
-
 static int push(fi_ring* r, const void* entries, size_t stride, int32_t n, void* ready, const char* who) {
     const std::string nm = who;
     FI_REQUIRE(r && entries, nm + ": null argument");
     FI_REQUIRE(n >= 1, nm + ": n = " + std::to_string(n) + " < 1");
     FI_HIP_CHECK(hipSetDevice(r->dev));
-    FI_TRY(check_source(r, entries, stride, n, nm));
+    // the checks fi_learner_step_entries_dev makes on its buffer
+    FI_TRY(check_entry_span(r->dev, entries, stride, n, r->entry, nm, "entry_bytes " + std::to_string(r->entry), "ring"));
     const uint64_t unread = r->head - r->tail, room = (uint64_t)r->C - unread;
     if ((uint64_t)n > room)
         return fail(FI_ERR_STATE, nm + ": full: " + std::to_string(n) + " entries, capacity " + std::to_string(r->C) +
@@ -311,8 +274,7 @@ int fi::ring_step_check(fi_learner* l, fi_ring* r, int32_t n_fresh, const std::s
     FI_TRY(learner_info(l, &li));
     FI_REQUIRE(li.dev == r->dev, nm + ": the ring's device " + std::to_string(r->dev) + " != the learner's " +
                                      std::to_string(li.dev));
-    FI_REQUIRE(li.dev_entries_ok, nm + ": an Atari handle reads device entries in the planes format only "
-                                       "(fi_learner_set_record_format(FI_RECORDS_PLANES) first)");
+    FI_TRY(require_dev_entries(li.dev_entries_ok, nm));
     const size_t need = fi_learner_entry_bytes(l);
     FI_REQUIRE(r->entry >= need, nm + ": the ring's entry_bytes " + std::to_string(r->entry) + " < " +
                                      std::to_string(need) + " = fi_learner_entry_bytes()");
@@ -335,33 +297,21 @@ int fi::ring_step_check(fi_learner* l, fi_ring* r, int32_t n_fresh, const std::s
 
 int fi::ring_step_entries(fi_ring* r, int B, const std::string& nm) {
     FI_HIP_CHECK(hipSetDevice(r->dev));
-    if (r->last_cap < B) {
-        if (r->last) {
-            FI_HIP_CHECK(hipStreamSynchronize(r->stream));  // behind the last step's columns kernel
-            (void)hipFree(r->last);
-            r->last = nullptr;
-            r->last_cap = r->last_n = 0;
-        }
-        const hipError_t e = hipMalloc((void**)&r->last, 8 * (size_t)B);
-        if (e != hipSuccess) {
-            r->last = nullptr;
-            (void)hipGetLastError();
-            return fail(FI_ERR_OOM, nm + ": hipMalloc(" + std::to_string(8 * (size_t)B) + ") for the entry indices");
-        }
-        r->last_cap = B;
+    if (r->last_cap >= B) return FI_OK;
+    if (r->last) {
+        FI_HIP_CHECK(hipStreamSynchronize(r->stream));  // behind the last step's columns kernel
+        r->last_n = 0;
     }
-    return FI_OK;
+    return dev_grow(&r->last, &r->last_cap, B, nm + ": the entry indices");
 }
 
-int fi::ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B, int rc) {
-    std::string why;
-    if (rc != FI_OK) why = fi_last_error();
+int fi::ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B) {
     // a later push may overwrite the slots this batch names: it goes behind the ingest
     FI_HIP_CHECK(hipStreamWaitEvent(r->stream, (hipEvent_t)fi_learner_entries_consumed_event(l), 0));
     r->tail += (uint64_t)n_fresh;
     r->draw += 1;
     r->last_n = B;
-    return rc == FI_OK ? FI_OK : fail(rc, why);
+    return FI_OK;
 }
 
 static int step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out, bool wait, const char* who) {
@@ -372,11 +322,9 @@ static int step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* 
     FI_TRY(ring_step_entries(r, li.B, nm));
     rb.entries_out = r->last;
     const int rc = learner_step_columns(l, r->have_pushed ? r->pushed : nullptr, learner_ring_ingest, &rb, out, wait, who);
-    // as fi_learner_step_rollouts: the batch counts as taken when the step ran (FI_ERR_NONFINITE: it
-    // ran and skipped its update) or, asynchronously, was enqueued; after any other status the
-    // counters stay
-    if (rc != FI_OK && rc != FI_ERR_NONFINITE) return rc;
-    return ring_step_taken(l, r, n_fresh, li.B, rc);
+    // as fi_learner_step_rollouts; after any other status the counters stay
+    if (!step_taken(rc)) return rc;
+    return finish_taken(rc, [&] { return ring_step_taken(l, r, n_fresh, li.B); });
 }
 
 extern "C" int fi_learner_step_ring(fi_learner* l, fi_ring* r, int32_t n_fresh, fi_step_stats* out) {

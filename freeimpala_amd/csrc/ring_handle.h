@@ -60,9 +60,9 @@ struct RingBatch {
 int ring_step_check(fi_learner* l, fi_ring* r, int32_t n_fresh, const std::string& nm, LearnerInfo* li, RingBatch* rb);
 // ring.hip: r->last for a batch of B columns
 int ring_step_entries(fi_ring* r, int B, const std::string& nm);
-// ring.hip: what follows a step that ran (rc: FI_OK or FI_ERR_NONFINITE) or was enqueued: the ring's
-// stream waits for the consumed event, the counters move; returns rc with its message restored
-int ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B, int rc);
+// ring.hip: the hand-back of a step that ran or was enqueued (host_util.h: step_taken, finish_taken):
+// the ring's stream waits for the consumed event, the counters move
+int ring_step_taken(fi_learner* l, fi_ring* r, int32_t n_fresh, int B);
 // weights.hip: the importance weights of a prioritised step (fi_weights.h), behind the draw that wrote
 // `entries` and the chunk sums on the same stream
 int prio_is_weights_launch(const uint64_t* entries, int B, int n_fresh, const uint32_t* table, int64_t C, uint64_t lo,
