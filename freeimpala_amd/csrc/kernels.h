@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "fi_diag.h"
 #include "fi_gather.h"
 #include "fi_learner.h"
 
@@ -210,6 +211,39 @@ int learner_publish_view(fi_learner* l, PublishView* out);
 // the block alone, an atomic load: the one thing of a learner another handle's thread may read
 void* learner_publish_block(const fi_learner* l);
 void learner_set_publish_block(fi_learner* l, void* block, void (*free_fn)(void*));
+
+// diag.hip: the off-policy diagnostics (include/fi_diag.h, where the rule stands). Workgroup (c, s)
+// of diag_plan()'s grid writes its partial sums into ws; one finalize workgroup adds them in a fixed
+// order and writes *out, col_kl and col_log_rho (nullable, B floats each) to device memory
+struct DiagPlan {
+    int column_tiles, time_slices, slice_len;  // slice s: the time steps [s * slice_len, min(T, (s + 1) * slice_len))
+};
+int diag_plan(int T, int B, int A, DiagPlan* out);
+size_t diag_workspace_bytes(int T, int B, int A);  // 0 for a refused shape
+int offpolicy_diag_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                          const float* disc, const float* val, const float* vs, const fi_vtrace_hparams& hp,
+                          fi_offpolicy_diag* out, float* col_kl, float* col_log_rho, void* ws, size_t ws_bytes,
+                          hipStream_t stream);
+
+// learner.cpp: what diag.hip reads of a learner, and where its diagnostics block hangs (as the
+// publication block does: learner.cpp names nothing of diag.hip, the block arrives with its free
+// function, which fi_learner_destroy calls behind the wait for the learner's streams)
+struct DiagView {
+    int dev, T, B, A;
+    const float* logits;  // (T+1, B, A): the first T * B rows are pi
+    const float* mu;
+    const int32_t* act;
+    const float* rew;
+    const float* disc;
+    const float* values;  // (T+1, B)
+    const float* vs;
+    fi_vtrace_hparams hp;
+    hipStream_t stream;
+    bool stepped;  // a step has been enqueued on the handle
+    void* block;
+};
+int learner_diag_view(fi_learner* l, DiagView* out);
+void learner_set_diag_block(fi_learner* l, void* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

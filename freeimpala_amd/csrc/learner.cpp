@@ -122,6 +122,11 @@ struct fi_learner {
     // function in with it; atomic because an actor's thread may look it up (fi_actor_set_params_dev)
     std::atomic<void*> publish{nullptr};
     void (*publish_free)(void*) = nullptr;
+    // the diagnostics block (fi_diag.h): made and freed by diag.hip in the same way; `stepped`: a step
+    // has been enqueued on the handle, so the loss tensors hold a step's values
+    void* diag = nullptr;
+    void (*diag_free)(void*) = nullptr;
+    bool stepped = false;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -221,6 +226,7 @@ static void destroy(fi_learner* l) {
     if (l->stream) hipStreamSynchronize(l->stream);
     if (l->copy_stream) hipStreamSynchronize(l->copy_stream);
     if (void* pb = l->publish.load()) l->publish_free(pb);
+    if (l->diag) l->diag_free(l->diag);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -740,6 +746,7 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
 extern "C" int fi_learner_step_resident(fi_learner* l, fi_step_stats* out) {
     FI_REQUIRE(l, "step: null learner");
     FI_HIP_CHECK(hipSetDevice(l->dev));
+    l->stepped = true;
     return guarded("step", FI_ERR_STATE, [&] { return run_step(l, nullptr, out); });
 }
 
@@ -864,6 +871,7 @@ static int stage_entries(fi_learner* l, const void* const* entries, size_t n_ent
 // statistics or not, and reports a batch it rejected; otherwise the step is enqueued only (no
 // sync) and fi_learner_wait reports it.
 static int finish_step(fi_learner* l, const BatchSource& src, fi_step_stats* out, bool wait) {
+    l->stepped = true;
     if (!wait) {
         FI_TRY(run_step(l, &src, nullptr));
         l->in_flight = true;
@@ -1243,6 +1251,20 @@ void* fi::learner_publish_block(const fi_learner* l) { return l ? l->publish.loa
 void fi::learner_set_publish_block(fi_learner* l, void* block, void (*free_fn)(void*)) {
     l->publish_free = free_fn;
     l->publish.store(block, std::memory_order_release);
+}
+
+// what diag.hip (fi_diag.h) reads of a learner: the tensors of the most recently enqueued step, the
+// thresholds and the stream; the block itself is diag.hip's
+int fi::learner_diag_view(fi_learner* l, DiagView* out) {
+    FI_REQUIRE(l && out, "learner_diag_view: null argument");
+    *out = DiagView{l->dev, l->T,  l->B,      l->A,  l->logits, l->mu,     l->act,     l->rew,
+                    l->disc, l->values, l->vs, l->cfg.hp, l->stream, l->stepped, l->diag};
+    return FI_OK;
+}
+
+void fi::learner_set_diag_block(fi_learner* l, void* block, void (*free_fn)(void*)) {
+    l->diag_free = free_fn;
+    l->diag = block;
 }
 
 // ------------------------------------------------------------------ params

@@ -295,6 +295,36 @@ class DeviceLearner:
         from . import publish
         return publish.lib().fi_publish_event(self._h)
 
+    # --- off-policy diagnostics of the most recent step (include/fi_diag.h; the rule: freeimpala_amd/diag.py)
+    def enqueue_diagnostics(self) -> None:
+        """Enqueue the diagnostics of the most recently enqueued step behind it on the learner's stream,
+        with the handle's thresholds; nothing waits. Steps enqueued afterwards do not disturb it."""
+        from . import diag
+        check(diag.lib().fi_diag_enqueue(self._h), "fi_diag_enqueue")
+
+    def _diag_call(self, fn, name: str, columns: bool) -> dict:
+        from . import diag
+        d = diag.OffPolicyDiag()
+        kl = np.empty(self.B, np.float32) if columns else None
+        lr = np.empty(self.B, np.float32) if columns else None
+        check(fn(self._h, C.byref(d), kl.ctypes.data if columns else None, lr.ctypes.data if columns else None, self.B),
+              name)
+        out = d.as_dict()
+        if columns:
+            out["col_kl"], out["col_log_rho"] = kl, lr
+        return out
+
+    def read_diagnostics(self, columns: bool = False) -> dict:
+        """Wait for the last ``enqueue_diagnostics`` alone and return its summary as a dict (the fields of
+        fi_offpolicy_diag); columns=True adds ``col_kl`` and ``col_log_rho``, (B,) float32."""
+        from . import diag
+        return self._diag_call(diag.lib().fi_diag_read, "fi_diag_read", columns)
+
+    def diagnostics(self, columns: bool = False) -> dict:
+        """``enqueue_diagnostics`` and ``read_diagnostics`` in one call."""
+        from . import diag
+        return self._diag_call(diag.lib().fi_diag_learner, "fi_diag_learner", columns)
+
     def step_segments_dev(self, segments, stats: bool = True) -> dict:
         """Step from segments of entries in device memory: (ptr, stride, n, event) tuples whose n sum
         to the batch; segment k fills the next n columns once its event (or None) has completed."""

@@ -34,6 +34,7 @@
 #include <thread>
 #include <vector>
 
+#include "fi_diag.h"
 #include "fi_learner.h"
 #include "fi_publish.h"
 #include "fi_train.h"
@@ -455,6 +456,24 @@ public:
         if (fi_publish_params(handles_[p], &tag) != FI_OK) return fail(p, fi_last_error());
         return true;
     }
+    // Off-policy diagnostics of player p's most recent step (include/fi_diag.h): rho statistics,
+    // KL(mu | pi), ESS, clip rates and the explained variance, reduced on the device beside the step.
+    // enqueue_diagnostics() only enqueues, behind the step on the learner's stream; read_diagnostics()
+    // waits for that result alone; diagnostics() is both. col_kl / col_log_rho (nullable): the per-column
+    // means, resized to the batch. With --data-parallel > 1 they describe shard 0.
+    bool enqueue_diagnostics(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        if (fi_diag_enqueue(handles_[p]) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool read_diagnostics(size_t p, fi_offpolicy_diag& out, std::vector<float>* col_kl = nullptr,
+                          std::vector<float>* col_log_rho = nullptr) {
+        return diag_call(p, fi_diag_read, out, col_kl, col_log_rho);
+    }
+    bool diagnostics(size_t p, fi_offpolicy_diag& out, std::vector<float>* col_kl = nullptr,
+                     std::vector<float>* col_log_rho = nullptr) {
+        return diag_call(p, fi_diag_learner, out, col_kl, col_log_rho);
+    }
     // --starting-model resume (Model::loadFromDisk bytes + version).
     bool load(size_t p, const std::vector<char>& blob, uint64_t version) {
         if (p >= handles_.size()) return fail(0, "player_index out of range");
@@ -477,6 +496,18 @@ public:
     const LearnerConfig& config() const { return cfg_; }
 
 private:
+    bool diag_call(size_t p, int (*fn)(fi_learner*, fi_offpolicy_diag*, float*, float*, int32_t), fi_offpolicy_diag& out,
+                   std::vector<float>* col_kl, std::vector<float>* col_log_rho) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const size_t B = cfg_.batch_size / (cfg_.data_parallel ? cfg_.data_parallel : 1);
+        if (col_kl) col_kl->resize(B);
+        if (col_log_rho) col_log_rho->resize(B);
+        if (fn(handles_[p], &out, col_kl ? col_kl->data() : nullptr, col_log_rho ? col_log_rho->data() : nullptr,
+               (int32_t)B) != FI_OK)
+            return fail(p, fi_last_error());
+        return true;
+    }
+
     // the fi_train.h calls the configuration asks for; none with the defaults
     bool apply_recipe(fi_learner* h) const {
         if (cfg_.optimizer == "rmsprop" &&

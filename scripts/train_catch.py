@@ -36,6 +36,11 @@ across the N environments, eps_i = EPS ** (1 + ALPHA i / (N - 1)). The records' 
 logits, so V-trace stays right; the scores are those of the exploring actors. The untrained baseline
 stays the plain draw. The defaults (1, 0, no ladder) leave the loop and the output unchanged; anything
 else writes profiles/train_catch_explore.json.
+
+`--diagnostics K` enqueues the off-policy diagnostics (include/fi_diag.h) behind the step of every K-th
+unroll and reads the newest one in front of the next report line: the clip rates, kl_mu_pi, ess, max_rho
+and explained_variance go to stderr and into the window's entry of the JSON
+(profiles/train_catch_diag.json unless --out names another file). The step is unchanged by it.
 """
 from __future__ import annotations
 
@@ -48,7 +53,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from freeimpala_amd import build_info, env, hip  # noqa: E402
+from freeimpala_amd import build_info, diag, env, hip  # noqa: E402
 from freeimpala_amd.actor import Actor  # noqa: E402
 from freeimpala_amd.learner import DeviceLearner  # noqa: E402
 
@@ -89,7 +94,7 @@ def explore(a: Actor, ex: dict | None) -> None:
         a.set_exploration(ex["temperature"], eps)
 
 
-def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = None) -> dict:
+def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = None, diag_every: int = 0) -> dict:
     """--publish device --overlap: unroll u + 1 is acted while unroll u is stepped; one host wait per window."""
     L = make_learner(config, unrolls)
     a = Actor("atari", N, num_actions=A, seed=SEED)
@@ -98,17 +103,19 @@ def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = N
     a.begin_rollout(T)
     e = env.CatchEnv(N, GAMMA, seed=SEED)
     assert e.rollout(a, T + 1) == T + 1  # the first unroll, complete
-    curve, seen, last = [], e.stats(), {}
+    curve, seen, last, pending = [], e.stats(), {}, 0
     t0 = time.perf_counter()
     for u in range(1, unrolls + 1):
         assert e.rollout(a, T - 1) == T - 1
         L.step_rollouts_async([a])
+        pending = diag.enqueue_every(L, u, diag_every) or pending  # --diagnostics K: no host wait
         hand_over(L, a, "device")
         assert e.rollout(a, 1) == 1
         if u % window == 0:
             last = L.wait()
             bv = L.batch_versions
             seen, w = window_of(e, seen)
+            pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4),
                               batch_versions=[bv["min"], bv["max"], round(bv["mean"], 3)], **w))
     last = L.wait()
@@ -122,7 +129,8 @@ def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = N
                 learner_version=last.get("version"), train_state=state)
 
 
-def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dict | None = None) -> dict:
+def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dict | None = None,
+          diag_every: int = 0) -> dict:
     L = make_learner(config, unrolls)
     a = Actor("atari", N, num_actions=A, seed=SEED)
     hand_over(L, a, publish)
@@ -130,14 +138,16 @@ def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dic
     a.begin_rollout(T)
     e = env.CatchEnv(N, GAMMA, seed=SEED)
     assert e.rollout(a, 1) == 1  # step 0 of the first unroll
-    curve, seen, last = [], e.stats(), {}
+    curve, seen, last, pending = [], e.stats(), {}, 0
     t0 = time.perf_counter()
     for u in range(1, unrolls + 1):
         assert e.rollout(a, T) == T
         last = L.step_rollout(a)
+        pending = diag.enqueue_every(L, u, diag_every) or pending  # --diagnostics K: no host wait
         hand_over(L, a, publish)
         if u % window == 0:
             seen, w = window_of(e, seen)
+            pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
     wall = time.perf_counter() - t0
     state = L.train_state()
@@ -177,7 +187,10 @@ def main() -> None:
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--epsilon", type=float, default=0.0)
     ap.add_argument("--epsilon-alpha", type=float, default=None)
+    ap.add_argument("--diagnostics", type=int, default=0, metavar="K")
     args = ap.parse_args()
+    if args.diagnostics < 0:
+        raise SystemExit("train_catch: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
     if args.overlap and args.publish != "device":
         raise SystemExit("train_catch: --overlap needs --publish device (the host blob waits for the learner)")
     default_mode = args.publish == "host" and not args.overlap
@@ -186,6 +199,8 @@ def main() -> None:
         ex = dict(temperature=args.temperature, epsilon=args.epsilon, epsilon_alpha=args.epsilon_alpha)
     elif args.epsilon_alpha is not None:
         raise SystemExit("train_catch: --epsilon-alpha is the ladder's exponent and needs --epsilon, its base")
+    if args.out is None and args.diagnostics:
+        args.out = os.path.join(ROOT, "profiles", "train_catch_diag.json")
     if args.out is None and ex:
         args.out = os.path.join(ROOT, "profiles", "train_catch_explore.json")
     if args.out is None:
@@ -195,9 +210,9 @@ def main() -> None:
     t0 = time.perf_counter()
     base = untrained(args.window)
     if args.overlap:
-        runs = {c: train_overlapped(c, args.unrolls, args.window, ex) for c in ("adam", "rmsprop")}
+        runs = {c: train_overlapped(c, args.unrolls, args.window, ex, args.diagnostics) for c in ("adam", "rmsprop")}
     else:
-        runs = {c: train(c, args.unrolls, args.window, args.publish, ex) for c in ("adam", "rmsprop")}
+        runs = {c: train(c, args.unrolls, args.window, args.publish, ex, args.diagnostics) for c in ("adam", "rmsprop")}
     res = dict(what="first learning measurement: the Atari policy on device-resident Catch, mean return of the episodes "
                     "finished in every window of unrolls; two documented settings, nothing tuned, no threshold",
                num_envs=N, batch=N, seq_len=T, num_actions=A, gamma=GAMMA, seed=SEED, unrolls=args.unrolls,
@@ -208,6 +223,8 @@ def main() -> None:
                source_hash=build_info.source_hash())
     if not default_mode:
         res.update(publish=args.publish, overlap=args.overlap)
+    if args.diagnostics:
+        res.update(diagnostics_every=args.diagnostics)
     if ex:
         res.update(exploration=dict(ex, note="the training actors explore and record their behaviour logits as mu; "
                                              "the scores are the exploring actors' own; the untrained baseline is the plain draw"))
