@@ -245,6 +245,37 @@ struct DiagView {
 int learner_diag_view(fi_learner* l, DiagView* out);
 void learner_set_diag_block(fi_learner* l, void* block, void (*free_fn)(void*));
 
+// popart.hip: PopArt value normalisation (include/fi_popart.h, where the rule stands). `state` is the
+// 32-byte device block {double mu, nu, sigma; uint64_t updates}; every kernel reads it there
+constexpr int kPopartStreamGridMax = 1024;  // workgroups of the two streaming kernels, at most
+int popart_plan(size_t n);                  // workgroups of the moments kernel: a fixed function of n
+size_t popart_workspace_bytes(size_t n);
+int popart_denorm_launch(float* values, size_t n, const void* state, hipStream_t s);
+int popart_scale_launch(float* dvalue, size_t n, const void* state, hipStream_t s);
+int popart_update_launch(const float* vs, size_t n, void* state, float* w, size_t w_stride, int H, float* b, double beta,
+                         double sigma_min, double sigma_max, const int* skip, void* ws, size_t ws_bytes, hipStream_t s);
+
+// learner.cpp: a learner's PopArt block, made and freed by popart.hip, which hands its launchers in
+// with it (as weights.hip hands in its ScaleFn): learner.cpp names nothing of popart.hip, so a
+// library of the learner alone links. run_step calls the three launchers while the block is there
+struct PopartBlock {
+    void* state = nullptr;  // device, 32 bytes
+    void* ws = nullptr;     // the moments workspace for T * B targets
+    size_t ws_bytes = 0;
+    double beta = 0.0, sigma_min = 0.0, sigma_max = 0.0;
+    int (*denorm)(float*, size_t, const void*, hipStream_t) = nullptr;
+    int (*scale)(float*, size_t, const void*, hipStream_t) = nullptr;
+    int (*update)(const float*, size_t, void*, float*, size_t, int, float*, double, double, double, const int*, void*,
+                  size_t, hipStream_t) = nullptr;
+};
+struct PopartView {
+    int dev, TB, nranks;
+    hipStream_t stream;
+    PopartBlock* block;
+};
+int learner_popart_view(fi_learner* l, PopartView* out);
+void learner_set_popart_block(fi_learner* l, PopartBlock* block, void (*free_fn)(void*));
+
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner
 struct ActorInfo {

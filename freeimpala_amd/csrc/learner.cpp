@@ -127,6 +127,9 @@ struct fi_learner {
     void* diag = nullptr;
     void (*diag_free)(void*) = nullptr;
     bool stepped = false;
+    // PopArt (fi_popart.h): the block is popart.hip's, with its launchers and its free function
+    PopartBlock* popart = nullptr;
+    void (*popart_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -227,6 +230,7 @@ static void destroy(fi_learner* l) {
     if (l->copy_stream) hipStreamSynchronize(l->copy_stream);
     if (void* pb = l->publish.load()) l->publish_free(pb);
     if (l->diag) l->diag_free(l->diag);
+    if (l->popart) l->popart_free(l->popart);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -634,6 +638,10 @@ static float lr_of(const fi_learner* l, uint64_t s) {
     return (float)((double)l->lr_base + ((double)l->lr_end - (double)l->lr_base) * (double)k / (double)l->lr_steps);
 }
 
+// the width of the layer under the heads: both policies end in (inputs x (A + 1)) weights, then A + 1
+// biases, with the value head in column A (mlp_forward; atari.hip's Offsets: hw, hb, fc width 512)
+static int head_inputs(const fi_learner* l) { return l->cfg.arch == FI_ARCH_ATARI ? 512 : l->H; }
+
 static BatchTensors batch_tensors(const fi_learner* l) {
     return BatchTensors{l->cfg.arch, l->T,   l->B,    l->A,   l->D,    l->obs,      l->frames, l->mu,
                         l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
@@ -665,6 +673,10 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         LearnerTagger tg(l);
         FI_TRY(atari_forward(l->atari, l->frames, l->logits, l->values, l->stream, l->profiling ? &tg : nullptr));
     }
+    if (l->popart) {  // the head predicts normalised values: everything behind this sees sigma n + mu
+        Tag t(l, "popart_denorm");
+        FI_TRY(l->popart->denorm(l->values, (size_t)l->rows, l->popart->state, l->stream));
+    }
     mark(l, FI_PHASE_VTRACE);
     int vt_nblk = 0;
     {
@@ -674,6 +686,10 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
                              l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue,
                              l->small, l->vt_ws, l->vt_ws_bytes, l->stream, false, &vt_nblk,
                              l->bad));
+    }
+    if (l->popart) {  // d/dv -> d/dn: one division by sigma; row T (no gradient) is not touched
+        Tag t(l, "popart_scale");
+        FI_TRY(l->popart->scale(l->dvalue, (size_t)l->TB, l->popart->state, l->stream));
     }
     // the loss is a plain sum over the columns: w_b times column b's gradient is the gradient of
     // sum_b w_b L_b (fi_weights.h). vs, pg_adv and the loss partials stay unweighted
@@ -712,6 +728,17 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         FI_TRY(optimizer_step(l->opt_kind, l->params, l->grads, l->opt_m, l->opt_v, l->nparams,
                               lr_of(l, (uint64_t)step), l->cfg.beta1, l->cfg.beta2, l->cfg.eps, bc1, bc2,
                               l->small + 3, l->cfg.max_grad_norm, l->stream, l->bad, &l->rms));
+    }
+    if (l->popart) {
+        // the statistics move with this step's targets and the value column is rewritten so that
+        // sigma n + mu is preserved; skipped with the update (the words the optimiser read)
+        Tag t(l, "popart_update");
+        const PopartBlock* pa = l->popart;
+        const int O = l->A + 1, Hh = head_inputs(l);
+        float* b = l->params + l->nparams - 1;                   // the last bias of the heads
+        float* w = l->params + l->nparams - O - (size_t)Hh * O + l->A;  // column A of the Hh x O weights
+        FI_TRY(pa->update(l->vs, (size_t)l->TB, pa->state, w, (size_t)O, Hh, b, pa->beta, pa->sigma_min, pa->sigma_max,
+                          l->bad, pa->ws, pa->ws_bytes, l->stream));
     }
     if (l->atari) {
         Tag t(l, "weights_bf16");
@@ -1265,6 +1292,18 @@ int fi::learner_diag_view(fi_learner* l, DiagView* out) {
 void fi::learner_set_diag_block(fi_learner* l, void* block, void (*free_fn)(void*)) {
     l->diag_free = free_fn;
     l->diag = block;
+}
+
+// what popart.hip (fi_popart.h) reads of a learner; the block itself is popart.hip's
+int fi::learner_popart_view(fi_learner* l, PopartView* out) {
+    FI_REQUIRE(l && out, "learner_popart_view: null argument");
+    *out = PopartView{l->dev, l->TB, l->comm ? l->nranks : 1, l->stream, l->popart};
+    return FI_OK;
+}
+
+void fi::learner_set_popart_block(fi_learner* l, PopartBlock* block, void (*free_fn)(void*)) {
+    l->popart_free = free_fn;
+    l->popart = block;
 }
 
 // ------------------------------------------------------------------ params

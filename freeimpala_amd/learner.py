@@ -263,6 +263,35 @@ class DeviceLearner:
         check(train.lib().fi_train_get_state(self._h, C.byref(st)), "fi_train_get_state")
         return st.as_dict()
 
+    # --- PopArt value normalisation (include/fi_popart.h; the rule: freeimpala_amd/popart.py)
+    def enable_popart(self, beta: float = 3e-4, sigma_min: float = 1e-4, sigma_max: float = 1e6) -> None:
+        """Every later step denormalises the value head's output with the statistics on the device,
+        divides the value gradient by sigma and, behind the optimiser, moves mu, sigma towards the
+        step's V-trace targets and rewrites the value column so that sigma n + mu is preserved. A
+        second call changes the three numbers and keeps the statistics; there is no disable."""
+        from . import popart
+        check(popart.lib().fi_popart_enable(self._h, beta, sigma_min, sigma_max), "fi_popart_enable")
+
+    def popart_state(self) -> dict:
+        """Wait for the stream and return enabled, beta, sigma_min, sigma_max, mu, nu, sigma, updates."""
+        from . import popart
+        st = popart.PopartState()
+        check(popart.lib().fi_popart_get_state(self._h, C.byref(st)), "fi_popart_get_state")
+        return st.as_dict()
+
+    def set_popart_state(self, mu: float, nu: float) -> None:
+        """Resume: store mu, nu and the sigma they imply; no weight is rewritten. Call order of a
+        resuming process: ``enable_popart``, ``set_popart_state``, ``load_state``."""
+        from . import popart
+        check(popart.lib().fi_popart_set_state(self._h, mu, nu), "fi_popart_set_state")
+
+    def popart_state_ptr(self) -> int:
+        """The device address of the 32-byte block {double mu, nu, sigma; uint64 updates}."""
+        from . import popart
+        p = C.c_void_p()
+        check(popart.lib().fi_popart_state_dev(self._h, C.byref(p)), "fi_popart_state_dev")
+        return int(p.value)
+
     # --- parameters published on the device (include/fi_publish.h)
     def publish(self) -> int:
         """Enqueue a publication of the parameters as they are at this point of the learner's stream

@@ -36,6 +36,7 @@
 
 #include "fi_diag.h"
 #include "fi_learner.h"
+#include "fi_popart.h"
 #include "fi_publish.h"
 #include "fi_train.h"
 
@@ -473,6 +474,30 @@ public:
     bool diagnostics(size_t p, fi_offpolicy_diag& out, std::vector<float>* col_kl = nullptr,
                      std::vector<float>* col_log_rho = nullptr) {
         return diag_call(p, fi_diag_learner, out, col_kl, col_log_rho);
+    }
+    // PopArt value normalisation on player p (include/fi_popart.h): every later step denormalises the
+    // value head's output with the statistics on the device, divides the value gradient by sigma and,
+    // behind the optimiser, moves mu, sigma and rewrites the value column so that sigma n + mu is
+    // preserved. The statistics are not in save_state()'s blob: a resuming process calls
+    // enable_popart, set_popart_state, then load_state. With --data-parallel > 1 the handles share a
+    // communicator and the call is refused.
+    bool enable_popart(size_t p, double beta = FI_POPART_BETA, double sigma_min = FI_POPART_SIGMA_MIN,
+                       double sigma_max = FI_POPART_SIGMA_MAX) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_popart_enable(h, beta, sigma_min, sigma_max) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool popart_state(size_t p, fi_popart_state& out) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        if (fi_popart_get_state(handles_[p], &out) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool set_popart_state(size_t p, double mu, double nu) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_popart_set_state(h, mu, nu) != FI_OK) return fail(p, fi_last_error());
+        return true;
     }
     // --starting-model resume (Model::loadFromDisk bytes + version).
     bool load(size_t p, const std::vector<char>& blob, uint64_t version) {

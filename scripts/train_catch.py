@@ -41,6 +41,12 @@ else writes profiles/train_catch_explore.json.
 unroll and reads the newest one in front of the next report line: the clip rates, kl_mu_pi, ess, max_rho
 and explained_variance go to stderr and into the window's entry of the JSON
 (profiles/train_catch_diag.json unless --out names another file). The step is unchanged by it.
+
+`--popart [BETA]` (include/fi_popart.h; BETA defaults to the paper's 3e-4) runs, next to the `rmsprop`
+configuration as it stands, `rmsprop_popart`: the same RMSProp numbers and schedule WITHOUT the reward
+clip and with PopArt value normalisation on the learner; `adam` is left out. Every window's entry of
+that run carries the statistics mu, sigma; the output goes to profiles/train_catch_popart.json unless --out
+names another file. Off by default: without the flag the loops enqueue what they enqueued before.
 """
 from __future__ import annotations
 
@@ -59,15 +65,19 @@ from freeimpala_amd.learner import DeviceLearner  # noqa: E402
 
 N, T, A, GAMMA, SEED = 256, 20, 3, 0.99, 1
 RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
+POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configuration
 
 
 def make_learner(config: str, unrolls: int) -> DeviceLearner:
-    if config == "rmsprop":
+    if config in ("rmsprop", "rmsprop_popart"):
         L = DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", optimizer="rmsprop",
                           lr=RMSPROP["lr"], seed=SEED)
         L.set_rmsprop(RMSPROP["decay"], RMSPROP["momentum"], RMSPROP["eps"])
         L.set_lr_schedule(0.0, unrolls)
-        L.set_reward_clip(RMSPROP["reward_clip"])
+        if config == "rmsprop_popart":  # the value head normalised in place of the clipped rewards
+            L.enable_popart(beta=POPART_BETA)
+        else:
+            L.set_reward_clip(RMSPROP["reward_clip"])
         return L
     return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
 
@@ -76,6 +86,14 @@ def window_of(e: env.CatchEnv, before: dict) -> tuple[dict, dict]:
     now = e.stats()
     n, s = now["episodes"] - before["episodes"], now["return_sum"] - before["return_sum"]
     return now, dict(episodes=n, mean_return=round(s / n, 4) if n else None)
+
+
+def popart_window(L: DeviceLearner, config: str) -> dict:
+    """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
+    if config != "rmsprop_popart":
+        return {}
+    s = L.popart_state()
+    return dict(popart_mu=round(s["mu"], 6), popart_sigma=round(s["sigma"], 6), popart_updates=s["updates"])
 
 
 def hand_over(L: DeviceLearner, a: Actor, publish: str) -> None:
@@ -115,6 +133,7 @@ def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = N
             last = L.wait()
             bv = L.batch_versions
             seen, w = window_of(e, seen)
+            w.update(popart_window(L, config))
             pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4),
                               batch_versions=[bv["min"], bv["max"], round(bv["mean"], 3)], **w))
@@ -147,6 +166,7 @@ def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dic
         hand_over(L, a, publish)
         if u % window == 0:
             seen, w = window_of(e, seen)
+            w.update(popart_window(L, config))
             pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
     wall = time.perf_counter() - t0
@@ -188,6 +208,7 @@ def main() -> None:
     ap.add_argument("--epsilon", type=float, default=0.0)
     ap.add_argument("--epsilon-alpha", type=float, default=None)
     ap.add_argument("--diagnostics", type=int, default=0, metavar="K")
+    ap.add_argument("--popart", type=float, nargs="?", const=3e-4, default=None, metavar="BETA")
     args = ap.parse_args()
     if args.diagnostics < 0:
         raise SystemExit("train_catch: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
@@ -199,6 +220,13 @@ def main() -> None:
         ex = dict(temperature=args.temperature, epsilon=args.epsilon, epsilon_alpha=args.epsilon_alpha)
     elif args.epsilon_alpha is not None:
         raise SystemExit("train_catch: --epsilon-alpha is the ladder's exponent and needs --epsilon, its base")
+    global POPART_BETA
+    if args.popart is not None and not 0.0 <= args.popart <= 1.0:
+        raise SystemExit("train_catch: --popart BETA is the statistics' step size, in [0, 1]")
+    POPART_BETA = args.popart
+    configs = ("adam", "rmsprop") if args.popart is None else ("rmsprop", "rmsprop_popart")
+    if args.out is None and args.popart is not None:
+        args.out = os.path.join(ROOT, "profiles", "train_catch_popart.json")
     if args.out is None and args.diagnostics:
         args.out = os.path.join(ROOT, "profiles", "train_catch_diag.json")
     if args.out is None and ex:
@@ -210,9 +238,9 @@ def main() -> None:
     t0 = time.perf_counter()
     base = untrained(args.window)
     if args.overlap:
-        runs = {c: train_overlapped(c, args.unrolls, args.window, ex, args.diagnostics) for c in ("adam", "rmsprop")}
+        runs = {c: train_overlapped(c, args.unrolls, args.window, ex, args.diagnostics) for c in configs}
     else:
-        runs = {c: train(c, args.unrolls, args.window, args.publish, ex, args.diagnostics) for c in ("adam", "rmsprop")}
+        runs = {c: train(c, args.unrolls, args.window, args.publish, ex, args.diagnostics) for c in configs}
     res = dict(what="first learning measurement: the Atari policy on device-resident Catch, mean return of the episodes "
                     "finished in every window of unrolls; two documented settings, nothing tuned, no threshold",
                num_envs=N, batch=N, seq_len=T, num_actions=A, gamma=GAMMA, seed=SEED, unrolls=args.unrolls,
@@ -225,6 +253,11 @@ def main() -> None:
         res.update(publish=args.publish, overlap=args.overlap)
     if args.diagnostics:
         res.update(diagnostics_every=args.diagnostics)
+    if args.popart is not None:
+        res["configs"].pop("adam")
+        res["configs"]["rmsprop_popart"] = dict({k: v for k, v in RMSPROP.items() if k != "reward_clip"}, lr_end=0.0,
+                                                lr_steps=args.unrolls, max_grad_norm="default (40)", reward_clip="off",
+                                                popart=dict(beta=args.popart, sigma_min=1e-4, sigma_max=1e6))
     if ex:
         res.update(exploration=dict(ex, note="the training actors explore and record their behaviour logits as mu; "
                                              "the scores are the exploring actors' own; the untrained baseline is the plain draw"))
