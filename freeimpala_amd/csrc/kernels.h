@@ -10,6 +10,7 @@
 #include "fi_diag.h"
 #include "fi_gather.h"
 #include "fi_learner.h"
+#include "fi_surrogate.h"
 
 namespace fi {
 
@@ -275,6 +276,44 @@ struct PopartView {
 };
 int learner_popart_view(fi_learner* l, PopartView* out);
 void learner_set_popart_block(fi_learner* l, PopartBlock* block, void (*free_fn)(void*));
+
+// surrogate.hip: the clipped surrogate policy loss on V-trace targets (include/fi_surrogate.h, where the
+// rule stands): rows, scan, loss and stats kernels in place of the V-trace launch. losses (nullable):
+// 3 doubles, the partials summed by the stats kernel; stats (nullable): the 32-byte block; bad
+// (nullable): as vtrace_launch's; tg (nullable): a tag around each launch, named after its kernel;
+// *partials, *nblk_out (nullable): the [nblk][3] loss partials inside ws, what grad_sqnorm adds
+struct KernelTagger;  // atari.h
+size_t surrogate_workspace_bytes(int T, int B, int A);  // 0 for a refused shape
+int surrogate_loss_blocks(int T, int B, int A);
+int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                     const float* disc, const float* val, const fi_vtrace_hparams& hp, const fi_surrogate_params& prm,
+                     float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
+                     int* bad, hipStream_t stream, KernelTagger* tg = nullptr, const double** partials = nullptr,
+                     int* nblk_out = nullptr);
+
+// learner.cpp: a learner's surrogate block, made and freed by surrogate.hip, which hands its launcher
+// in with it (as popart.hip does): learner.cpp names nothing of surrogate.hip, so a library of the
+// learner alone links. While the block is there and `on`, run_step calls `launch` where it launches
+// V-trace and hands *partials, *nblk to grad_sqnorm
+struct SurrogateBlock {
+    void* stats = nullptr;  // device, 32 bytes
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    bool on = false;
+    float clip = 0.f, adv_eps = 0.f;
+    uint32_t normalize = 0;
+    int (*launch)(const SurrogateBlock*, int T, int B, int A, const float* pi, const float* mu, const int32_t* act,
+                  const float* rew, const float* disc, const float* val, const fi_vtrace_hparams& hp, float* vs, float* adv,
+                  float* dlog, float* dval, int* bad, hipStream_t stream, KernelTagger* tg, const double** partials,
+                  int* nblk) = nullptr;
+};
+struct SurrogateView {
+    int dev, T, B, A, nranks;
+    hipStream_t stream;
+    SurrogateBlock* block;
+};
+int learner_surrogate_view(fi_learner* l, SurrogateView* out);
+void learner_set_surrogate_block(fi_learner* l, SurrogateBlock* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

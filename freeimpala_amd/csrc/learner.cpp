@@ -130,6 +130,9 @@ struct fi_learner {
     // PopArt (fi_popart.h): the block is popart.hip's, with its launchers and its free function
     PopartBlock* popart = nullptr;
     void (*popart_free)(void*) = nullptr;
+    // the clipped surrogate objective (fi_surrogate.h): the block is surrogate.hip's, with its launcher
+    SurrogateBlock* surrogate = nullptr;
+    void (*surrogate_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -231,6 +234,7 @@ static void destroy(fi_learner* l) {
     if (void* pb = l->publish.load()) l->publish_free(pb);
     if (l->diag) l->diag_free(l->diag);
     if (l->popart) l->popart_free(l->popart);
+    if (l->surrogate) l->surrogate_free(l->surrogate);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -679,13 +683,21 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     }
     mark(l, FI_PHASE_VTRACE);
     int vt_nblk = 0;
-    {
+    const double* loss_part = nullptr;  // [vt_nblk][3], summed by the gradient-norm kernel
+    if (l->surrogate && l->surrogate->on) {
+        // the second objective (fi_surrogate.h) in V-trace's place: the same outputs, its own tags
+        LearnerTagger tg(l);
+        FI_TRY(l->surrogate->launch(l->surrogate, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc, l->values,
+                                    l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue, l->bad, l->stream,
+                                    l->profiling ? &tg : nullptr, &loss_part, &vt_nblk));
+    } else {
         // scan + loss + gradients; the loss partials are summed by the gradient-norm kernel
         Tag t(l, "vtrace");
         FI_TRY(vtrace_launch(0, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc,
                              l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue,
                              l->small, l->vt_ws, l->vt_ws_bytes, l->stream, false, &vt_nblk,
                              l->bad));
+        loss_part = vtrace_partials(l->vt_ws);
     }
     if (l->popart) {  // d/dv -> d/dn: one division by sigma; row T (no gradient) is not touched
         Tag t(l, "popart_scale");
@@ -717,7 +729,7 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     {
         Tag t(l, "grad_norm");  // + the V-trace loss sums (losses land in small[0..2])
         FI_TRY(grad_sqnorm(l->grads, l->nparams, l->small + 8, kSqParts, l->small + 3, l->stream,
-                           vtrace_partials(l->vt_ws), vt_nblk, l->small, l->bad + 1));
+                           loss_part, vt_nblk, l->small, l->bad + 1));
     }
     const int step = l->step_count + 1;
     const double bc1 = 1.0 - std::pow((double)l->cfg.beta1, step);
@@ -1304,6 +1316,18 @@ int fi::learner_popart_view(fi_learner* l, PopartView* out) {
 void fi::learner_set_popart_block(fi_learner* l, PopartBlock* block, void (*free_fn)(void*)) {
     l->popart_free = free_fn;
     l->popart = block;
+}
+
+// what surrogate.hip (fi_surrogate.h) reads of a learner; the block itself is surrogate.hip's
+int fi::learner_surrogate_view(fi_learner* l, SurrogateView* out) {
+    FI_REQUIRE(l && out, "learner_surrogate_view: null argument");
+    *out = SurrogateView{l->dev, l->T, l->B, l->A, l->comm ? l->nranks : 1, l->stream, l->surrogate};
+    return FI_OK;
+}
+
+void fi::learner_set_surrogate_block(fi_learner* l, SurrogateBlock* block, void (*free_fn)(void*)) {
+    l->surrogate_free = free_fn;
+    l->surrogate = block;
 }
 
 // ------------------------------------------------------------------ params

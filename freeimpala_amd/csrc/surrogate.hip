@@ -1,0 +1,735 @@
+// surrogate.hip -- the clipped surrogate policy loss on V-trace targets (include/fi_surrogate.h, where
+// the rule stands): the kernels that take the place of the V-trace launch of a step, and every
+// fi_surrogate_* entry point.
+//
+//   surrogate_rows_kernel   a stream over (t, b), diag.hip's read pattern: workgroup (c, s) owns the 64
+//                           columns of tile c and the time steps of slice s, its four waves the steps
+//                           t .. t + 3 of a round, lane = column. The pi and mu rows of one (t, tile) are
+//                           one contiguous run: read 16 bytes per lane and access into padded LDS rows
+//                           (stride A | 1 floats: no bank conflicts), then one lane per row. Writes
+//                           d = rho^ (r + g V' - V), k = g c and log rho per row; counts bad actions.
+//   surrogate_scan_kernel   acc_t = d_t + k_t acc_{t+1} down each column, one lane per column, one wave
+//                           per workgroup (64 workgroups at B = 4096, spread over the CUs). The five loads
+//                           of the next eight time steps are issued before the dependent chain of the
+//                           current eight runs. Writes vs, A and one fp64 pair of moment partials.
+//   surrogate_loss_kernel   the rows kernel's grid and read pattern over pi alone. Every workgroup adds
+//                           the moment partials itself, in one fixed order: no finalize launch stands
+//                           between the scan and the loss. dlogits are written over the lane's own pi
+//                           row in LDS and leave as the run's 16-byte pieces. The three loss sums and the
+//                           clipped count are reduced per wave by DPP / permlane: one partial per workgroup.
+//   surrogate_stats_kernel  one workgroup: the clipped counts of all workgroups added in a fixed order
+//                           and the 32-byte stats block (a count over the whole grid cannot be written
+//                           by workgroup 0 of the loss kernel without an atomic or a grid-wide wait);
+//                           for the stand-alone entry also the three loss scalars.
+// No float atomics; the bad-action count is an integer atomic, as V-trace's. learner.cpp names nothing
+// of this file: fi_surrogate_enable hangs a SurrogateBlock with the launcher on the handle (kernels.h).
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "atari.h"  // KernelTagger, TagScope
+#include "fi_common.h"
+#include "fi_surrogate.h"
+#include "host_util.h"
+#include "kernels.h"
+
+namespace fi {
+
+namespace {
+constexpr int kCols = 64;          // columns per workgroup: lane = column
+constexpr int kWaves = 4;          // waves per workgroup of the two streams: one time step each per round
+constexpr int kTargetWgs = 768;    // three workgroups per CU at B = 4096: the slices of T fill the chip
+constexpr int kPiecesPerLane = 5;  // 16-byte pieces a lane has in flight per tensor (A = 18: 4.5 per lane and run)
+constexpr int kAhead = 8;          // time steps of the scan whose loads are in flight ahead of the chain
+constexpr int kStatThreads = 256;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct StatsBlock {
+    uint64_t rows, rows_clipped;
+    double adv_mean, adv_std;
+};
+static_assert(sizeof(StatsBlock) == 32, "fi_surrogate.h fixes the block at 32 bytes");
+
+struct SurArgs {
+    int T, B, A;
+    int ct, slices, slice_len, nscan;
+    const float* __restrict__ pi;
+    const float* __restrict__ mu;
+    const int32_t* __restrict__ act;
+    const float* __restrict__ rew;
+    const float* __restrict__ disc;
+    const float* __restrict__ val;
+    float* vs;
+    float* adv;
+    float* dlog;
+    float* dval;
+    float* d;                     // workspace: [T * B] each
+    float* k;
+    float* lr;
+    double* mom;                  // [nscan][2]: sums of A - pivot and of its square
+    double* pivot;                // 1
+    double* part;                 // [ct * slices][3]
+    unsigned long long* clipped;  // [ct * slices]
+    int* bad;
+    fi_vtrace_hparams hp;
+    float clip, adv_eps;
+    uint32_t normalize;
+};
+
+// Wave-wide sum of a double in VALU cross-lane moves (diag.hip's wave_reduce): rotations 8, 4, 2, 1
+// inside each 16-lane row by DPP, then the row pairs and halves by v_permlane16_swap /
+// v_permlane32_swap. The order is fixed; every lane ends with the result.
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)u, CTRL, 0xf, 0xf, false);
+    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+template <int S>
+__device__ __forceinline__ double xor_d(double v, int lane) {  // v of lane ^ S, S = 16 or 32
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
+    unsigned rlo, rhi;
+    if constexpr (S == 16) {
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        rlo = (lane & 16) ? a[0] : a[1];
+        rhi = (lane & 16) ? b[0] : b[1];
+    } else {
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        rlo = (lane & 32) ? a[0] : a[1];
+        rhi = (lane & 32) ? b[0] : b[1];
+    }
+    return __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
+}
+__device__ __forceinline__ double wave_reduce(double v, int lane) {
+    v += dpp_d<0x128>(v);  // row_ror:8
+    v += dpp_d<0x124>(v);  // row_ror:4
+    v += dpp_d<0x122>(v);  // row_ror:2
+    v += dpp_d<0x121>(v);  // row_ror:1
+    v += xor_d<16>(v, lane);
+    v += xor_d<32>(v, lane);
+    return v;
+}
+
+// N sums of a workgroup of NW waves through LDS (red: NW * N doubles), the waves added in ascending
+// order; every thread gets the results. A barrier stands in front of the writes, so red may have been
+// read just before.
+template <int N, int NW>
+__device__ __forceinline__ void block_sums(double (&v)[N], double* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_reduce(v[i], lane);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) red[w * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = red[i];
+#pragma unroll
+        for (int w2 = 1; w2 < NW; ++w2) s += red[w2 * N + i];
+        v[i] = s;
+    }
+}
+
+// m and s of A from the scan's partials: thread i adds the partials i, i + 256, ... in ascending order,
+// then block_sums. The loss kernel's workgroups and the stats kernel run this same sequence on the same
+// numbers, so they hold the same bits. n = 1 gives s = 0 exactly: S2 / 1 and (S1 / 1)^2 are one product.
+__device__ __forceinline__ void moments(const SurArgs& a, double* red, double& m, double& s) {
+    static_assert(kStatThreads == 64 * kWaves, "the loss and the stats kernel share this reduction");
+    double v[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < a.nscan; i += kStatThreads) {
+        v[0] += a.mom[2 * i];
+        v[1] += a.mom[2 * i + 1];
+    }
+    block_sums<2, kWaves>(v, red);
+    const double n = (double)a.T * (double)a.B;
+    const double m1 = v[0] / n, var = v[1] / n - m1 * m1;
+    m = *a.pivot + m1;
+    s = sqrt(var > 0.0 ? var : (var == var ? 0.0 : var));  // NaN stays NaN
+}
+
+// The run of nb * A floats of one (t, tile) from global memory into the wave's padded LDS rows, 16
+// bytes per lane and access, consecutive lanes consecutive pieces; a head and a tail of up to 3 floats
+// where the run does not start or end on a 16-byte boundary. g0 < 2^31 (the launcher's check).
+template <bool kMu>
+__device__ __forceinline__ void load_run(const float* __restrict__ pi, const float* __restrict__ mu, float* __restrict__ lp,
+                                         float* __restrict__ lm, uint32_t g0, uint32_t n, uint32_t A, uint32_t S, int lane) {
+    const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
+    const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
+    const float* __restrict__ gp = pi + g0;
+    const float* __restrict__ gm = mu + g0;
+    const f32x4* __restrict__ gp4 = (const f32x4*)(gp + head);  // 16-byte aligned: (g0 + head) % 4 == 0
+    const f32x4* __restrict__ gm4 = (const f32x4*)(gm + head);
+    for (uint32_t k0 = 0; k0 < nbody; k0 += 64u * kPiecesPerLane) {
+        f32x4 vp[kPiecesPerLane], vm[kPiecesPerLane];
+#pragma unroll
+        for (int u = 0; u < kPiecesPerLane; ++u) {
+            const uint32_t p = k0 + 64u * u + lane;
+            if (p < nbody) {
+                vp[u] = __builtin_nontemporal_load(gp4 + p);
+                if (kMu) vm[u] = __builtin_nontemporal_load(gm4 + p);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kPiecesPerLane; ++u) {
+            const uint32_t p = k0 + 64u * u + lane;
+            if (p < nbody) {
+                const uint32_t e = head + 4u * p;
+                uint32_t r = e / A, cc = e - r * A;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    lp[r * S + cc] = vp[u][j];
+                    if (kMu) lm[r * S + cc] = vm[u][j];
+                    if (++cc == A) {
+                        cc = 0u;
+                        ++r;
+                    }
+                }
+            }
+        }
+    }
+    if ((uint32_t)lane < head) {
+        const uint32_t r = (uint32_t)lane / A, cc = (uint32_t)lane - r * A;
+        lp[r * S + cc] = gp[lane];
+        if (kMu) lm[r * S + cc] = gm[lane];
+    }
+    if ((uint32_t)lane < tail) {
+        const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
+        lp[r * S + cc] = gp[e];
+        if (kMu) lm[r * S + cc] = gm[e];
+    }
+}
+
+// the reverse: the wave's padded LDS rows leave as the run's 16-byte pieces
+__device__ __forceinline__ void store_run(float* __restrict__ out, const float* __restrict__ lp, uint32_t g0, uint32_t n,
+                                          uint32_t A, uint32_t S, int lane) {
+    const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
+    const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
+    float* __restrict__ go = out + g0;
+    f32x4* __restrict__ go4 = (f32x4*)(go + head);
+    for (uint32_t p = lane; p < nbody; p += 64u) {
+        const uint32_t e = head + 4u * p;
+        uint32_t r = e / A, cc = e - r * A;
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = lp[r * S + cc];
+            if (++cc == A) {
+                cc = 0u;
+                ++r;
+            }
+        }
+        go4[p] = v;
+    }
+    if ((uint32_t)lane < head) {
+        const uint32_t r = (uint32_t)lane / A, cc = (uint32_t)lane - r * A;
+        go[lane] = lp[r * S + cc];
+    }
+    if ((uint32_t)lane < tail) {
+        const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
+        go[e] = lp[r * S + cc];
+    }
+}
+
+constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+}  // namespace
+
+__global__ __launch_bounds__(64 * kWaves) void surrogate_rows_kernel(SurArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char ssm[];
+    const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
+    const int c = (int)blockIdx.x % a.ct, s = (int)blockIdx.x / a.ct;
+    const int T = a.T, B = a.B;
+    const uint32_t A = (uint32_t)a.A, S = A | 1u;
+    const int b0 = c * kCols, nb = min(kCols, B - b0);
+    const int t_lo = s * a.slice_len, t_hi = min(T, t_lo + a.slice_len);
+    float* const lp = (float*)ssm + (size_t)w * 2 * kCols * S;  // this wave's pi rows, then its mu rows
+    float* const lm = lp + kCols * S;
+    const uint32_t n = (uint32_t)nb * A;
+    int nbad = 0;
+    for (int t0 = t_lo; t0 < t_hi; t0 += kWaves) {
+        const int t = t0 + w;
+        const bool live = t < t_hi;  // wave-uniform
+        const bool mine = live && lane < nb;
+        int at = 0;
+        float rw = 0.f, g = 1.f, v = 0.f, vn = 0.f;
+        if (mine) {
+            const size_t e = (size_t)t * B + b0 + lane;
+            at = a.act[e];
+            rw = a.rew[e];
+            g = a.disc[e];
+            v = a.val[e];
+            vn = a.val[e + B];
+        }
+        if (live) load_run<true>(a.pi, a.mu, lp, lm, ((uint32_t)t * (uint32_t)B + (uint32_t)b0) * A, n, A, S, lane);
+        __syncthreads();  // the rows are in LDS (a wave reads its own rows only; the round count is uniform)
+        if (mine) {
+            const float* __restrict__ zp = lp + (uint32_t)lane * S;
+            const float* __restrict__ zm = lm + (uint32_t)lane * S;
+            if ((unsigned)at >= A) ++nbad;
+            const uint32_t ai = at < 0 ? 0u : ((uint32_t)at >= A ? A - 1u : (uint32_t)at);
+            // x = {pi side, mu side}: one instruction sequence for both
+            f32x2 mx = {zp[0], zm[0]};
+            for (uint32_t i = 1; i < A; ++i) mx = __builtin_elementwise_max(mx, f32x2{zp[i], zm[i]});
+            f32x2 se = {0.f, 0.f};
+            for (uint32_t i = 0; i < A; ++i) {
+                const f32x2 x = (f32x2{zp[i], zm[i]} - mx) * L2E;
+                se += f32x2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+            }
+            const f32x2 lg = f32x2{__builtin_amdgcn_logf(se.x), __builtin_amdgcn_logf(se.y)} * LN2;
+            const f32x2 la = (f32x2{zp[ai], zm[ai]} - mx) - lg;  // log pi(a), log mu(a)
+            const float lr = la.x - la.y;
+            const float rho = __expf(lr);
+            const size_t e = (size_t)t * B + b0 + lane;
+            a.d[e] = fminf(a.hp.rho_bar, rho) * (rw + g * vn - v);
+            a.k[e] = g * (a.hp.lambda_ * fminf(a.hp.c_bar, rho));
+            a.lr[e] = lr;
+        }
+        __syncthreads();  // the rows are read: the next round may overwrite them
+    }
+    const unsigned long long any = __ballot(nbad != 0);
+    if (any) {  // wave-uniform; the rare path
+        int tot = nbad;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+        if (lane == 0) atomicAdd(a.bad, tot);
+    }
+}
+
+// One wave per workgroup, lane = column. cur / nxt: the loads of eight time steps each; the next
+// eight are issued before the chain over the current eight, so the chain never waits for a load it
+// could have had. Steps below t = 0 load row 0 again and are not used.
+__global__ __launch_bounds__(64) void surrogate_scan_kernel(SurArgs a) {
+    const int lane = threadIdx.x, b = (int)blockIdx.x * kCols + lane;
+    const int T = a.T, B = a.B;
+    const bool mine = b < B;
+    const int bb = mine ? b : B - 1;
+    double pivot;
+    {
+        const float p = a.rew[0] + a.disc[0] * a.val[B] - a.val[0];
+        pivot = fabsf(p) <= 3.0e38f ? (double)p : 0.0;
+    }
+    if (blockIdx.x == 0 && lane == 0) *a.pivot = pivot;
+    struct Step {
+        float d, k, r, g, v;
+    };
+    auto load = [&](int t) {
+        const size_t e = (size_t)(t < 0 ? 0 : t) * B + bb;
+        return Step{a.d[e], a.k[e], a.rew[e], a.disc[e], a.val[e]};
+    };
+    Step cur[kAhead], nxt[kAhead];
+#pragma unroll
+    for (int j = 0; j < kAhead; ++j) cur[j] = load(T - 1 - j);
+    float acc = 0.f, vs_next = a.val[(size_t)T * B + bb];
+    double s1 = 0.0, s2 = 0.0;
+    for (int t1 = T - 1; t1 >= 0; t1 -= kAhead) {
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) nxt[j] = load(t1 - kAhead - j);
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+            const int t = t1 - j;
+            if (t >= 0) {  // uniform
+                const Step x = cur[j];
+                acc = x.d + x.k * acc;
+                const float vs = x.v + acc;
+                const float adv = x.r + x.g * vs_next - x.v;
+                vs_next = vs;
+                if (mine) {
+                    const size_t e = (size_t)t * B + b;
+                    a.vs[e] = vs;
+                    a.adv[e] = adv;
+                    const double q = (double)adv - pivot;
+                    s1 += q;
+                    s2 += q * q;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) cur[j] = nxt[j];
+    }
+    s1 = wave_reduce(s1, lane);
+    s2 = wave_reduce(s2, lane);
+    if (lane == 0) {
+        a.mom[2 * (size_t)blockIdx.x] = s1;
+        a.mom[2 * (size_t)blockIdx.x + 1] = s2;
+    }
+}
+
+__global__ __launch_bounds__(64 * kWaves) void surrogate_loss_kernel(SurArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char ssm[];
+    __shared__ double red[kWaves * 4];
+    const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
+    const int c = (int)blockIdx.x % a.ct, s = (int)blockIdx.x / a.ct;
+    const int T = a.T, B = a.B;
+    const uint32_t A = (uint32_t)a.A, S = A | 1u;
+    const int b0 = c * kCols, nb = min(kCols, B - b0);
+    const int t_lo = s * a.slice_len, t_hi = min(T, t_lo + a.slice_len);
+    float* const lp = (float*)ssm + (size_t)w * kCols * S;  // this wave's pi rows, dlogits after the arithmetic
+    const uint32_t n = (uint32_t)nb * A;
+    double m = 0.0, sd = 1.0;
+    if (a.normalize) moments(a, red, m, sd);  // uniform over the grid
+    const double den = sd + (double)a.adv_eps;
+    const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
+    const float bc = a.hp.baseline_cost, ec = a.hp.entropy_cost;
+    if (s == 0 && tid < nb) a.dval[(size_t)T * B + b0 + tid] = 0.f;  // the bootstrap row has no gradient
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};  // L_pg, baseline, entropy, clipped rows
+    for (int t0 = t_lo; t0 < t_hi; t0 += kWaves) {
+        const int t = t0 + w;
+        const bool live = t < t_hi;  // wave-uniform
+        const bool mine = live && lane < nb;
+        const uint32_t g0 = ((uint32_t)t * (uint32_t)B + (uint32_t)b0) * A;
+        int at = 0;
+        float lr = 0.f, adv = 0.f, v = 0.f, vs = 0.f;
+        if (mine) {
+            const size_t e = (size_t)t * B + b0 + lane;
+            at = a.act[e];
+            lr = a.lr[e];
+            adv = a.adv[e];
+            v = a.val[e];
+            vs = a.vs[e];
+        }
+        if (live) load_run<false>(a.pi, nullptr, lp, nullptr, g0, n, A, S, lane);
+        __syncthreads();  // the rows are in LDS
+        if (mine) {
+            float* __restrict__ z = lp + (uint32_t)lane * S;
+            const uint32_t ai = at < 0 ? 0u : ((uint32_t)at >= A ? A - 1u : (uint32_t)at);
+            const float rho = __expf(lr);
+            const float an = a.normalize ? (float)(((double)adv - m) / den) : adv;
+            const bool clipped = (an > 0.f && rho > hi) || (an < 0.f && rho < lo);
+            const float rc = fminf(fmaxf(rho, lo), hi);
+            const float g = clipped ? 0.f : -rho * an;
+            float mx = z[0];
+            for (uint32_t i = 1; i < A; ++i) mx = fmaxf(mx, z[i]);
+            float se = 0.f, sed = 0.f;
+            for (uint32_t i = 0; i < A; ++i) {
+                const float d = z[i] - mx, e = __builtin_amdgcn_exp2f(d * L2E);
+                se += e;
+                sed += e * d;
+            }
+            const float lg = __builtin_amdgcn_logf(se) * LN2;
+            const float plogp = sed / se - lg;  // sum pi log pi
+            for (uint32_t i = 0; i < A; ++i) {
+                const float d = z[i] - mx, p = __builtin_amdgcn_exp2f(d * L2E) / se;
+                z[i] = g * ((i == ai ? 1.f : 0.f) - p) + ec * p * ((d - lg) - plogp);
+            }
+            const float td = v - vs;
+            a.dval[(size_t)t * B + b0 + lane] = bc * td;
+            sum[0] += (double)(-fminf(rho * an, rc * an));
+            sum[1] += 0.5 * (double)td * (double)td;
+            sum[2] += (double)plogp;
+            sum[3] += clipped ? 1.0 : 0.0;
+        }
+        __syncthreads();  // the dlogits rows are complete
+        if (live) store_run(a.dlog, lp, g0, n, A, S, lane);
+        __syncthreads();  // the rows have left: the next round may overwrite them
+    }
+    block_sums<4, kWaves>(sum, red);
+    if (tid < 3) a.part[(size_t)blockIdx.x * 3 + tid] = sum[tid];
+    if (tid == 3) a.clipped[blockIdx.x] = (unsigned long long)sum[3];
+}
+
+// One workgroup: the stats block (nullable) and, for the stand-alone entry, the loss scalars (nullable;
+// NaN when an action was outside [0, A): that entry has no synchronous status to return).
+__global__ __launch_bounds__(kStatThreads) void surrogate_stats_kernel(SurArgs a, void* stats, double* losses) {
+    __shared__ double red[kWaves * 4];
+    double m, sd;
+    moments(a, red, m, sd);
+    const int nblk = a.ct * a.slices;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += kStatThreads) {
+        v[0] += a.part[(size_t)i * 3];
+        v[1] += a.part[(size_t)i * 3 + 1];
+        v[2] += a.part[(size_t)i * 3 + 2];
+        v[3] += (double)a.clipped[i];
+    }
+    block_sums<4, kWaves>(v, red);
+    if (threadIdx.x != 0) return;
+    if (stats) {
+        StatsBlock* o = (StatsBlock*)stats;
+        o->rows = (uint64_t)a.T * (uint64_t)a.B;
+        o->rows_clipped = (uint64_t)v[3];
+        o->adv_mean = m;
+        o->adv_std = sd;
+    }
+    if (losses) {
+        const bool poisoned = *a.bad != 0;
+        for (int i = 0; i < 3; ++i) losses[i] = poisoned ? __builtin_nan("") : v[i];
+    }
+}
+
+// ------------------------------------------------------------------ the launcher
+namespace {
+struct Plan {
+    int ct, slices, slice_len, nscan;
+};
+
+int plan_of(int T, int B, int A, Plan* out) {
+    FI_REQUIRE(T >= 1 && B >= 1, "surrogate: T = " + std::to_string(T) + ", B = " + std::to_string(B) + " must be >= 1");
+    FI_REQUIRE(A >= 2 && A <= 64, "surrogate: A = " + std::to_string(A) + " outside 2 .. 64");
+    FI_REQUIRE((uint64_t)T * (uint64_t)B * (uint64_t)A < (1ull << 31),
+               "surrogate: T * B * A = " + std::to_string((uint64_t)T * (uint64_t)B * (uint64_t)A) + " passes 2^31 - 1");
+    const int ct = (B + kCols - 1) / kCols;
+    const int want = (kTargetWgs + ct - 1) / ct, most = (T + kWaves - 1) / kWaves;  // a slice holds a round at least
+    const int s0 = want < most ? want : most;
+    int len = (T + s0 - 1) / s0;
+    len = (len + kWaves - 1) / kWaves * kWaves;
+    *out = Plan{ct, (T + len - 1) / len, len, ct};
+    return FI_OK;
+}
+
+size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// workspace: d | k | log rho (T * B floats each) | moment partials | pivot | loss partials | clipped
+// counts | the stand-alone entry's bad-action counter; every part on a 256-byte boundary
+struct Layout {
+    size_t row, mom, pivot, part, clipped, bad, total;
+};
+Layout layout_of(int T, int B, const Plan& p) {
+    Layout l{};
+    const size_t nblk = (size_t)p.ct * p.slices;
+    l.row = pad256((size_t)T * B * sizeof(float));
+    l.mom = 3 * l.row;
+    l.pivot = l.mom + pad256((size_t)p.nscan * 2 * sizeof(double));
+    l.part = l.pivot + 256;
+    l.clipped = l.part + pad256(nblk * 3 * sizeof(double));
+    l.bad = l.clipped + pad256(nblk * sizeof(unsigned long long));
+    l.total = l.bad + 256;
+    return l;
+}
+
+// more than 64 KB of dynamic LDS (A > 30 for the rows kernel, A = 63, 64 for the loss kernel): the
+// kernel's limit is raised once per device (a bit per device id)
+int raise_lds(const void* fn, std::atomic<uint64_t>& raised, size_t most) {
+    int dev = 0;
+    FI_HIP_CHECK(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;
+    if (!bit || !(raised.load(std::memory_order_acquire) & bit)) {
+        FI_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+        raised.fetch_or(bit, std::memory_order_acq_rel);
+    }
+    return FI_OK;
+}
+
+int check_params(const std::string& who, const fi_surrogate_params* p) {
+    FI_REQUIRE(p, who + ": null params");
+    FI_REQUIRE(std::isfinite(p->clip) && p->clip > 0.f, who + ": clip " + std::to_string(p->clip) + " must be finite and > 0");
+    FI_REQUIRE(std::isfinite(p->adv_eps) && p->adv_eps >= 0.f,
+               who + ": adv_eps " + std::to_string(p->adv_eps) + " must be finite and >= 0");
+    FI_REQUIRE(p->normalize <= 1u, who + ": normalize " + std::to_string(p->normalize) + " is neither 0 nor 1");
+    return FI_OK;
+}
+}  // namespace
+
+size_t surrogate_workspace_bytes(int T, int B, int A) {
+    Plan p{};
+    return plan_of(T, B, A, &p) == FI_OK ? layout_of(T, B, p).total : 0;
+}
+
+int surrogate_loss_blocks(int T, int B, int A) {
+    Plan p{};
+    return plan_of(T, B, A, &p) == FI_OK ? p.ct * p.slices : 0;
+}
+
+int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                     const float* disc, const float* val, const fi_vtrace_hparams& hp, const fi_surrogate_params& prm,
+                     float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
+                     int* bad, hipStream_t stream, KernelTagger* tg, const double** partials, int* nblk_out) {
+    FI_REQUIRE(pi && mu && act && rew && disc && val && vs && adv && dlog && dval && ws, "surrogate: null argument");
+    Plan p{};
+    FI_TRY(plan_of(T, B, A, &p));
+    FI_REQUIRE((uintptr_t)pi % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)dlog % 16 == 0,
+               "surrogate: pi, mu and dlogits must be 16-byte aligned (16 bytes move per lane and access)");
+    FI_REQUIRE((uintptr_t)act % 4 == 0 && (uintptr_t)rew % 4 == 0 && (uintptr_t)disc % 4 == 0 && (uintptr_t)val % 4 == 0 &&
+                   (uintptr_t)vs % 4 == 0 && (uintptr_t)adv % 4 == 0 && (uintptr_t)dval % 4 == 0 && (uintptr_t)bad % 4 == 0,
+               "surrogate: act, rew, disc, val, vs, adv, dvalue and bad must be 4-byte aligned");
+    FI_REQUIRE((uintptr_t)losses % 8 == 0 && (uintptr_t)stats % 8 == 0 && (uintptr_t)ws % 8 == 0,
+               "surrogate: losses, stats_dev and ws must be 8-byte aligned");
+    const Layout lay = layout_of(T, B, p);
+    FI_REQUIRE(ws_bytes >= lay.total, "surrogate: ws_bytes " + std::to_string(ws_bytes) + " < " + std::to_string(lay.total) +
+                                          " = fi_surrogate_workspace_bytes(" + std::to_string(T) + ", " + std::to_string(B) +
+                                          ", " + std::to_string(A) + ")");
+    char* w = (char*)ws;
+    SurArgs a{};
+    a.T = T, a.B = B, a.A = A;
+    a.ct = p.ct, a.slices = p.slices, a.slice_len = p.slice_len, a.nscan = p.nscan;
+    a.pi = pi, a.mu = mu, a.act = act, a.rew = rew, a.disc = disc, a.val = val;
+    a.vs = vs, a.adv = adv, a.dlog = dlog, a.dval = dval;
+    a.d = (float*)w, a.k = (float*)(w + lay.row), a.lr = (float*)(w + 2 * lay.row);
+    a.mom = (double*)(w + lay.mom), a.pivot = (double*)(w + lay.pivot), a.part = (double*)(w + lay.part);
+    a.clipped = (unsigned long long*)(w + lay.clipped);
+    a.bad = bad;
+    a.hp = hp;
+    a.clip = prm.clip, a.adv_eps = prm.adv_eps, a.normalize = prm.normalize;
+    if (!bad) {  // stand-alone: count into the workspace
+        a.bad = (int*)(w + lay.bad);
+        FI_HIP_CHECK(hipMemsetAsync(a.bad, 0, sizeof(int), stream));
+    }
+    const unsigned nblk = (unsigned)(p.ct * p.slices);
+    const size_t row_bytes = (size_t)kWaves * kCols * (A | 1) * sizeof(float), row_most = (size_t)kWaves * kCols * 65 * 4;
+    if (2 * row_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        FI_TRY(raise_lds((const void*)surrogate_rows_kernel, raised, 2 * row_most));
+    }
+    if (row_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        FI_TRY(raise_lds((const void*)surrogate_loss_kernel, raised, row_most));
+    }
+    {
+        TagScope t(tg, "surrogate_rows");
+        hipLaunchKernelGGL(surrogate_rows_kernel, dim3(nblk), dim3(64 * kWaves), 2 * row_bytes, stream, a);
+        FI_HIP_CHECK(hipGetLastError());
+    }
+    {
+        TagScope t(tg, "surrogate_scan");
+        hipLaunchKernelGGL(surrogate_scan_kernel, dim3((unsigned)p.nscan), dim3(64), 0, stream, a);
+        FI_HIP_CHECK(hipGetLastError());
+    }
+    {
+        TagScope t(tg, "surrogate_loss");
+        hipLaunchKernelGGL(surrogate_loss_kernel, dim3(nblk), dim3(64 * kWaves), row_bytes, stream, a);
+        FI_HIP_CHECK(hipGetLastError());
+    }
+    if (stats || losses) {
+        TagScope t(tg, "surrogate_stats");
+        hipLaunchKernelGGL(surrogate_stats_kernel, dim3(1), dim3(kStatThreads), 0, stream, a, stats, losses);
+        FI_HIP_CHECK(hipGetLastError());
+    }
+    if (partials) *partials = a.part;
+    if (nblk_out) *nblk_out = (int)nblk;
+    return FI_OK;
+}
+
+// ------------------------------------------------------------------ the learner's block
+namespace {
+int block_launch(const SurrogateBlock* b, int T, int B, int A, const float* pi, const float* mu, const int32_t* act,
+                 const float* rew, const float* disc, const float* val, const fi_vtrace_hparams& hp, float* vs, float* adv,
+                 float* dlog, float* dval, int* bad, hipStream_t stream, KernelTagger* tg, const double** partials,
+                 int* nblk) {
+    const fi_surrogate_params prm{b->clip, b->normalize, b->adv_eps, 0u};
+    return surrogate_launch(T, B, A, pi, mu, act, rew, disc, val, hp, prm, vs, adv, dlog, dval, nullptr, b->stats, b->ws,
+                            b->ws_bytes, bad, stream, tg, partials, nblk);
+}
+
+void block_free(void* p) {
+    SurrogateBlock* b = (SurrogateBlock*)p;
+    if (!b) return;
+    if (b->stats) (void)hipFree(b->stats);
+    if (b->ws) (void)hipFree(b->ws);
+    delete b;
+}
+
+int block_create(const SurrogateView& v, SurrogateBlock** out) {
+    SurrogateBlock* b = new (std::nothrow) SurrogateBlock();
+    FI_REQUIRE(b, "surrogate_enable: out of host memory");
+    b->launch = block_launch;
+    b->ws_bytes = surrogate_workspace_bytes(v.T, v.B, v.A);
+    int rc = b->ws_bytes ? FI_OK : fail(FI_ERR_INVALID, "surrogate_enable: the learner's shape is outside the kernels' (" +
+                                                            std::string(fi_last_error()) + ")");
+    if (rc == FI_OK) rc = dev_alloc(&b->stats, sizeof(StatsBlock), "surrogate_enable: stats block");
+    if (rc == FI_OK) rc = dev_alloc(&b->ws, b->ws_bytes, "surrogate_enable: workspace");
+    if (rc == FI_OK) {
+        const hipError_t e = hipMemsetAsync(b->stats, 0, sizeof(StatsBlock), v.stream);
+        if (e != hipSuccess || hipStreamSynchronize(v.stream) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(FI_ERR_HIP, "surrogate_enable: clearing the stats block failed");
+        }
+    }
+    if (rc != FI_OK) {
+        block_free(b);
+        return rc;
+    }
+    *out = b;
+    return FI_OK;
+}
+}  // namespace
+
+}  // namespace fi
+
+using namespace fi;
+
+extern "C" int fi_surrogate_enable(fi_learner* l, const fi_surrogate_params* params) {
+    FI_REQUIRE(l, "surrogate_enable: null learner");
+    FI_TRY(check_params("surrogate_enable", params));
+    SurrogateView v{};
+    FI_TRY(learner_surrogate_view(l, &v));
+    if (params->normalize && v.nranks > 1)
+        return fail(FI_ERR_STATE, "surrogate_enable: the handle is attached to a communicator of " + std::to_string(v.nranks) +
+                                      " ranks; the advantage moments of a normalising step would need an all-reduce");
+    SurrogateBlock* b = v.block;
+    if (!b) {
+        FI_HIP_CHECK(hipSetDevice(v.dev));
+        FI_TRY(guarded("surrogate_enable", FI_ERR_OOM, [&] { return block_create(v, &b); }));
+        learner_set_surrogate_block(l, b, block_free);
+    }
+    b->clip = params->clip;  // by value into every later launch
+    b->normalize = params->normalize;
+    b->adv_eps = params->adv_eps;
+    b->on = true;
+    return FI_OK;
+}
+
+extern "C" int fi_surrogate_disable(fi_learner* l) {
+    FI_REQUIRE(l, "surrogate_disable: null learner");
+    SurrogateView v{};
+    FI_TRY(learner_surrogate_view(l, &v));
+    if (v.block) v.block->on = false;
+    return FI_OK;
+}
+
+extern "C" int fi_surrogate_get_state(fi_learner* l, fi_surrogate_state* out) {
+    FI_REQUIRE(l && out, "surrogate_get_state: null argument");
+    SurrogateView v{};
+    FI_TRY(learner_surrogate_view(l, &v));
+    std::memset(out, 0, sizeof(*out));
+    out->clip = FI_SURROGATE_CLIP;
+    out->adv_eps = FI_SURROGATE_ADV_EPS;
+    const SurrogateBlock* b = v.block;
+    if (!b) return FI_OK;
+    StatsBlock st{};
+    FI_HIP_CHECK(hipSetDevice(v.dev));
+    FI_HIP_CHECK(hipMemcpyAsync(&st, b->stats, sizeof(st), hipMemcpyDeviceToHost, v.stream));
+    FI_HIP_CHECK(hipStreamSynchronize(v.stream));
+    out->enabled = b->on ? 1u : 0u;
+    out->normalize = b->normalize;
+    out->clip = b->clip;
+    out->adv_eps = b->adv_eps;
+    out->rows = st.rows;
+    out->rows_clipped = st.rows_clipped;
+    out->adv_mean = st.adv_mean;
+    out->adv_std = st.adv_std;
+    return FI_OK;
+}
+
+extern "C" int fi_surrogate_stats_dev(fi_learner* l, const void** ptr) {
+    FI_REQUIRE(l && ptr, "surrogate_stats_dev: null argument");
+    SurrogateView v{};
+    FI_TRY(learner_surrogate_view(l, &v));
+    if (!v.block)
+        return fail(FI_ERR_STATE, "surrogate_stats_dev: the objective was never on on this handle (fi_surrogate_enable first)");
+    *ptr = v.block->stats;
+    return FI_OK;
+}
+
+extern "C" size_t fi_surrogate_workspace_bytes(int T, int B, int A) { return surrogate_workspace_bytes(T, B, A); }
+extern "C" int fi_surrogate_loss_blocks(int T, int B, int A) { return surrogate_loss_blocks(T, B, A); }
+
+extern "C" int fi_surrogate_loss_fp32(int T, int B, int A, const float* pi, const float* mu, const int32_t* act,
+                                      const float* rew, const float* disc, const float* val, const fi_vtrace_hparams* hp,
+                                      const fi_surrogate_params* params, float* vs, float* adv, float* dlogits, float* dvalue,
+                                      double* losses, void* stats_dev, void* ws, size_t ws_bytes, int* bad, void* stream) {
+    FI_REQUIRE(hp, "surrogate_loss: null hparams");
+    FI_TRY(check_params("surrogate_loss", params));
+    return surrogate_launch(T, B, A, pi, mu, act, rew, disc, val, *hp, *params, vs, adv, dlogits, dvalue, losses, stats_dev,
+                            ws, ws_bytes, bad, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}

@@ -292,6 +292,39 @@ class DeviceLearner:
         check(popart.lib().fi_popart_state_dev(self._h, C.byref(p)), "fi_popart_state_dev")
         return int(p.value)
 
+    # --- the learner's objective (include/fi_surrogate.h; the rule: freeimpala_amd/surrogate.py)
+    def set_objective(self, name: str = "vtrace", clip: float = 0.2, normalize_advantages: bool = False,
+                      adv_eps: float = 1e-8) -> None:
+        """"surrogate": every later step runs the clipped surrogate -min(rho A, clip(rho, 1 - clip, 1 + clip) A)
+        on V-trace's targets in place of the V-trace policy gradient, with the advantages normalised over the
+        batch when asked; a second call replaces the numbers. "vtrace": the V-trace step again, bit for bit.
+        Between any two steps."""
+        from . import surrogate
+        if name == "vtrace":
+            check(surrogate.lib().fi_surrogate_disable(self._h), "fi_surrogate_disable")
+        elif name == "surrogate":
+            prm = surrogate.params(clip, normalize_advantages, adv_eps)
+            check(surrogate.lib().fi_surrogate_enable(self._h, C.byref(prm)), "fi_surrogate_enable")
+        else:
+            raise ValueError(f"objective: vtrace | surrogate, not {name!r}")
+
+    def objective_state(self) -> dict:
+        """Wait for the stream and return objective ("vtrace" | "surrogate"), clip, normalize, adv_eps and the
+        last surrogate step's stats block: rows, rows_clipped, adv_mean, adv_std."""
+        from . import surrogate
+        st = surrogate.SurrogateState()
+        check(surrogate.lib().fi_surrogate_get_state(self._h, C.byref(st)), "fi_surrogate_get_state")
+        d = st.as_dict()
+        d["objective"] = "surrogate" if d.pop("enabled") else "vtrace"
+        return d
+
+    def surrogate_stats_ptr(self) -> int:
+        """The device address of the 32-byte block {uint64 rows, rows_clipped; double adv_mean, adv_std}."""
+        from . import surrogate
+        p = C.c_void_p()
+        check(surrogate.lib().fi_surrogate_stats_dev(self._h, C.byref(p)), "fi_surrogate_stats_dev")
+        return int(p.value)
+
     # --- parameters published on the device (include/fi_publish.h)
     def publish(self) -> int:
         """Enqueue a publication of the parameters as they are at this point of the learner's stream

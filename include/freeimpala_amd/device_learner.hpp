@@ -38,6 +38,7 @@
 #include "fi_learner.h"
 #include "fi_popart.h"
 #include "fi_publish.h"
+#include "fi_surrogate.h"
 #include "fi_train.h"
 
 namespace freeimpala_amd {
@@ -497,6 +498,29 @@ public:
         if (p >= handles_.size()) return fail(0, "player_index out of range");
         for (fi_learner* h : shards_[p])
             if (fi_popart_set_state(h, mu, nu) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    // The clipped surrogate objective on player p (include/fi_surrogate.h): every later step runs
+    // -min(rho A, clip(rho, 1 - clip, 1 + clip) A) on V-trace's targets in place of the V-trace policy
+    // gradient, until clear_surrogate(). With --data-parallel > 1 the handles share a communicator and
+    // normalize_advantages is refused (the moments would need an all-reduce); plain clipping is fine.
+    bool set_surrogate(size_t p, float clip = FI_SURROGATE_CLIP, bool normalize_advantages = false,
+                       float adv_eps = FI_SURROGATE_ADV_EPS) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const fi_surrogate_params prm{clip, normalize_advantages ? 1u : 0u, adv_eps, 0u};
+        for (fi_learner* h : shards_[p])
+            if (fi_surrogate_enable(h, &prm) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool clear_surrogate(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_surrogate_disable(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool surrogate_state(size_t p, fi_surrogate_state& out) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        if (fi_surrogate_get_state(handles_[p], &out) != FI_OK) return fail(p, fi_last_error());
         return true;
     }
     // --starting-model resume (Model::loadFromDisk bytes + version).

@@ -49,6 +49,14 @@ configuration as it stands, `rmsprop_popart`: the same RMSProp numbers and sched
 clip and with PopArt value normalisation on the learner; `adam` is left out. Every window's entry of
 that run carries the statistics mu, sigma; the output goes to profiles/train_breakout_popart.json unless --out
 names another file. Off by default: without the flag the loops enqueue what they enqueued before.
+
+`--objective surrogate` (include/fi_surrogate.h; `--clip EPS`, default 0.2) runs, next to the `rmsprop`
+configuration as it stands (the V-trace policy gradient), `rmsprop_surrogate`: the same numbers, schedule and
+reward clip with the clipped surrogate objective on the learner; `--normalize-adv` adds
+`rmsprop_surrogate_normalized`, the same with the advantages normalised over the batch; `adam` is left out.
+Every window's entry of those runs carries the last step's clipped fraction and advantage moments; the output
+goes to profiles/train_breakout_surrogate.json unless --out names another file. The default, `--objective
+vtrace`, leaves the loops as they were.
 """
 from __future__ import annotations
 
@@ -68,10 +76,11 @@ from freeimpala_amd.learner import DeviceLearner  # noqa: E402
 N, T, A, GAMMA, SEED, MAX_STEPS = 256, 20, 3, 0.99, 1, 1000
 RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
 POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configuration
+SURROGATE_CLIP = 0.2  # --clip EPS: the eps of the rmsprop_surrogate* configurations
 
 
 def make_learner(config: str, unrolls: int) -> DeviceLearner:
-    if config in ("rmsprop", "rmsprop_popart"):
+    if config.startswith("rmsprop"):
         L = DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", optimizer="rmsprop",
                           lr=RMSPROP["lr"], seed=SEED)
         L.set_rmsprop(RMSPROP["decay"], RMSPROP["momentum"], RMSPROP["eps"])
@@ -80,6 +89,8 @@ def make_learner(config: str, unrolls: int) -> DeviceLearner:
             L.enable_popart(beta=POPART_BETA)
         else:
             L.set_reward_clip(RMSPROP["reward_clip"])
+        if "surrogate" in config:  # the second objective in V-trace's place; everything else as `rmsprop`
+            L.set_objective("surrogate", clip=SURROGATE_CLIP, normalize_advantages=config.endswith("_normalized"))
         return L
     return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
 
@@ -92,6 +103,10 @@ def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
 
 def popart_window(L: DeviceLearner, config: str) -> dict:
     """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
+    if "surrogate" in config:
+        s = L.objective_state()
+        return dict(clipped_fraction=round(s["rows_clipped"] / max(1, s["rows"]), 4), adv_mean=round(s["adv_mean"], 6),
+                    adv_std=round(s["adv_std"], 6))
     if config != "rmsprop_popart":
         return {}
     s = L.popart_state()
@@ -211,6 +226,9 @@ def main() -> None:
     ap.add_argument("--epsilon-alpha", type=float, default=None)
     ap.add_argument("--diagnostics", type=int, default=0, metavar="K")
     ap.add_argument("--popart", type=float, nargs="?", const=3e-4, default=None, metavar="BETA")
+    ap.add_argument("--objective", choices=("vtrace", "surrogate"), default="vtrace")
+    ap.add_argument("--clip", type=float, default=0.2, metavar="EPS")
+    ap.add_argument("--normalize-adv", action="store_true")
     args = ap.parse_args()
     if args.diagnostics < 0:
         raise SystemExit("train_breakout: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
@@ -227,6 +245,18 @@ def main() -> None:
         raise SystemExit("train_breakout: --popart BETA is the statistics' step size, in [0, 1]")
     POPART_BETA = args.popart
     configs = ("adam", "rmsprop") if args.popart is None else ("rmsprop", "rmsprop_popart")
+    global SURROGATE_CLIP
+    if args.objective == "surrogate":
+        if args.popart is not None:
+            raise SystemExit("train_breakout: --objective surrogate and --popart are separate comparisons; run them apart")
+        if not 0.0 < args.clip < float("inf"):
+            raise SystemExit("train_breakout: --clip EPS is the surrogate's clip range, finite and > 0")
+        SURROGATE_CLIP = args.clip
+        configs = ("rmsprop", "rmsprop_surrogate") + (("rmsprop_surrogate_normalized",) if args.normalize_adv else ())
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "train_breakout_surrogate.json")
+    elif args.normalize_adv or args.clip != 0.2:
+        raise SystemExit("train_breakout: --clip and --normalize-adv belong to --objective surrogate")
     if args.out is None and args.popart is not None:
         args.out = os.path.join(ROOT, "profiles", "train_breakout_popart.json")
     if args.out is None and args.diagnostics:
@@ -261,6 +291,12 @@ def main() -> None:
         res["configs"]["rmsprop_popart"] = dict({k: v for k, v in RMSPROP.items() if k != "reward_clip"}, lr_end=0.0,
                                                 lr_steps=args.unrolls, max_grad_norm="default (40)", reward_clip="off",
                                                 popart=dict(beta=args.popart, sigma_min=1e-4, sigma_max=1e6))
+    if args.objective == "surrogate":
+        res["configs"].pop("adam")
+        for c in configs[1:]:
+            res["configs"][c] = dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)",
+                                     objective=dict(name="surrogate", clip=args.clip, adv_eps=1e-8,
+                                                    normalize_advantages=c.endswith("_normalized")))
     if ex:
         res.update(exploration=dict(ex, note="the training actors explore and record their behaviour logits as mu; "
                                              "the scores are the exploring actors' own; the untrained baseline is the plain draw"))
