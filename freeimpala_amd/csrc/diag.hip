@@ -3,18 +3,11 @@
 // value head's explained variance, reduced on the device from the tensors a step leaves there. It
 // runs beside the step, never inside it: learner.cpp names nothing of this file (kernels.h).
 //
-//   * offpolicy_diag_kernel: a pure read stream, (8 A + 24) bytes per (t, b). Workgroup (c, s) owns
-//     the 64 columns [64 c, 64 c + 64) and the time steps of slice s; its four waves take the time
-//     steps t, t + 1, t + 2, t + 3 of a round, lane = column. The pi and mu rows of one (t, tile) are
-//     one contiguous run of nb * A floats in global memory: the wave reads it 16 bytes per lane and
-//     access, consecutive lanes consecutive pieces (a head and a tail of up to 3 floats where the run
-//     does not start or end on a 16-byte boundary: A = 3, 18 and odd B * A occur), and stores it into
-//     its own LDS rows; then every lane computes its own row out of LDS. Row stride in LDS: A | 1
-//     floats. ds_read_b32 is served in two groups of 32 lanes over 32 banks, so a stride of A floats is
-//     a 2-way conflict at A = 18 and a 32-way one at A = 64 in each group; an odd stride maps the 32
-//     lanes of a group to 32 different banks. The padding costs the 16-byte LDS store (a padded row
-//     does not start on a 16-byte boundary): the pieces go in as four ds_write_b32, which is not what
-//     limits a kernel that moves 69 MB through HBM.
+//   * offpolicy_diag_kernel: a pure read stream, (8 A + 24) bytes per (t, b), in row_stream.h's
+//     pattern: workgroup (c, s) owns the 64 columns [64 c, 64 c + 64) and the time steps of slice s;
+//     its four waves take the time steps t, t + 1, t + 2, t + 3 of a round, lane = column. The pi and
+//     mu rows of one (t, tile) arrive in the wave's padded LDS rows (load_run<true>); then every lane
+//     computes its own row out of LDS.
 //     act / rew / disc / val / vs: 4 bytes per lane, 256 contiguous bytes per wave and tensor.
 //     Per-row arithmetic is fp32 with vtrace.hip's intrinsics (v_exp_f32, v_log_f32), the pi and the
 //     mu side as the two lanes of one 2-vector, so both get the same instruction sequence. Every
@@ -36,14 +29,11 @@
 #include "fi_diag.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "row_stream.h"  // kCols, kWaves, load_run, wave_reduce, combine, tile_plan
 
 namespace fi {
 
 namespace {
-constexpr int kCols = 64;         // columns per workgroup: lane = column
-constexpr int kWaves = 4;         // waves per workgroup: one time step each per round
-constexpr int kTargetWgs = 768;   // three workgroups per CU at B = 4096: the slices of T fill the chip
-constexpr int kPiecesPerLane = 5; // 16-byte pieces a lane has in flight per tensor (A = 18: 4.5 per lane and run)
 constexpr int kFinalThreads = 1024;
 
 // the sums a workgroup hands on beside its per-column ones
@@ -54,9 +44,6 @@ enum {
     S_MAX_RHO = S_SUMS, S_MIN_RHO, S_COUNT
 };
 enum { C_USED, C_KL, C_LR, C_COUNT };  // per column
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct DiagArgs {
     int T, B, A;
@@ -73,61 +60,13 @@ struct DiagArgs {
     float rho_bar, c_bar, pg_rho_bar;
 };
 
-// float e of a run -> its place in the wave's padded LDS rows
-__device__ __forceinline__ void put(float* __restrict__ lp, float* __restrict__ lm, uint32_t e, uint32_t A, uint32_t S,
-                                    float p, float m) {
-    const uint32_t r = e / A, c = e - r * A;
-    lp[r * S + c] = p;
-    lm[r * S + c] = m;
-}
-
-// Wave-wide reduction of a double in VALU cross-lane moves, vtrace.hip's vt_wave_sum with the
-// operator as a parameter: rotations 8, 4, 2, 1 inside each 16-lane row by DPP, then the row pairs
-// and halves by v_permlane16_swap / v_permlane32_swap. No trip through the LDS crossbar, which a
-// shuffle takes (ds_bpermute): with some twenty doubles per wave to reduce, shuffles cost the two
-// launches 6 us of 46 at T = 100, B = 4096 and 8 of 23 at T = 20, B = 256 (scripts/diag_bench.py,
-// before and after). The order is fixed; every lane ends with the result.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)u, CTRL, 0xf, 0xf, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-template <int S>
-__device__ __forceinline__ double xor_d(double v, int lane) {  // v of lane ^ S, S = 16 or 32
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    unsigned rlo, rhi;
-    if constexpr (S == 16) {
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        rlo = (lane & 16) ? a[0] : a[1];
-        rhi = (lane & 16) ? b[0] : b[1];
-    } else {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        rlo = (lane & 32) ? a[0] : a[1];
-        rhi = (lane & 32) ? b[0] : b[1];
-    }
-    return __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
-}
-enum { OP_SUM, OP_MAX, OP_MIN };
-// op is a constant wherever this is called (an unrolled loop's index decides it), so the selects fold
-__device__ __forceinline__ double combine(int op, double x, double y) {
-    return op == OP_SUM ? x + y : (op == OP_MAX ? fmax(x, y) : fmin(x, y));
-}
-__device__ __forceinline__ double wave_reduce(int op, double v, int lane) {
-    v = combine(op, v, dpp_d<0x128>(v));  // row_ror:8
-    v = combine(op, v, dpp_d<0x124>(v));  // row_ror:4
-    v = combine(op, v, dpp_d<0x122>(v));  // row_ror:2
-    v = combine(op, v, dpp_d<0x121>(v));  // row_ror:1
-    v = combine(op, v, xor_d<16>(v, lane));
-    v = combine(op, v, xor_d<32>(v, lane));
-    return v;
-}
-// how entry i of a workgroup's sums (S_*) combines: added, or an extreme
+// how entry i of a workgroup's sums (S_*) combines: added, or an extreme (row_stream.h's operators)
 __device__ __forceinline__ constexpr int op_of(int i) { return i < S_SUMS ? OP_SUM : (i == S_MAX_RHO ? OP_MAX : OP_MIN); }
+// row_stream.h's wave reduction for an operator that an unrolled loop's index decides: op is a constant
+// at every call, so one of the three is left
+__device__ __forceinline__ double wave_reduce_op(int op, double v, int lane) {
+    return op == OP_SUM ? wave_reduce<OP_SUM>(v, lane) : (op == OP_MAX ? wave_reduce<OP_MAX>(v, lane) : wave_reduce<OP_MIN>(v, lane));
+}
 
 // the var(vs) sums run on vs - pivot: a variance does not depend on the shift, a constant vs gives
 // exactly 0 and nothing cancels for a vs far from 0
@@ -149,7 +88,6 @@ __global__ __launch_bounds__(64 * kWaves) void offpolicy_diag_kernel(DiagArgs a)
     float* const lm = lp + kCols * S;
     const uint32_t n = (uint32_t)nb * A;  // floats of a run
     const float pivot = vs_pivot(a.vs);
-    constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
     double col[C_COUNT] = {0.0, 0.0, 0.0};
     double acc[S_COUNT];
@@ -172,49 +110,7 @@ __global__ __launch_bounds__(64 * kWaves) void offpolicy_diag_kernel(DiagArgs a)
             v = a.val[e];
             vt = a.vs[e];
         }
-        if (live) {
-            // the run of this (t, tile): g0 < 2^31 (the launcher's check), so 32-bit indices do
-            const uint32_t g0 = ((uint32_t)t * (uint32_t)B + (uint32_t)b0) * A;
-            const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
-            const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
-            const float* __restrict__ gp = a.pi + g0;
-            const float* __restrict__ gm = a.mu + g0;
-            const f32x4* __restrict__ gp4 = (const f32x4*)(gp + head);  // 16-byte aligned: (g0 + head) % 4 == 0
-            const f32x4* __restrict__ gm4 = (const f32x4*)(gm + head);
-            for (uint32_t k0 = 0; k0 < nbody; k0 += 64u * kPiecesPerLane) {
-                f32x4 vp[kPiecesPerLane], vm[kPiecesPerLane];
-#pragma unroll
-                for (int u = 0; u < kPiecesPerLane; ++u) {
-                    const uint32_t p = k0 + 64u * u + lane;
-                    if (p < nbody) {
-                        vp[u] = __builtin_nontemporal_load(gp4 + p);
-                        vm[u] = __builtin_nontemporal_load(gm4 + p);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < kPiecesPerLane; ++u) {
-                    const uint32_t p = k0 + 64u * u + lane;
-                    if (p < nbody) {
-                        const uint32_t e = head + 4u * p;
-                        uint32_t r = e / A, cc = e - r * A;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            lp[r * S + cc] = vp[u][j];
-                            lm[r * S + cc] = vm[u][j];
-                            if (++cc == A) {
-                                cc = 0u;
-                                ++r;
-                            }
-                        }
-                    }
-                }
-            }
-            if ((uint32_t)lane < head) put(lp, lm, lane, A, S, gp[lane], gm[lane]);
-            if ((uint32_t)lane < tail) {
-                const uint32_t e = head + 4u * nbody + lane;
-                put(lp, lm, e, A, S, gp[e], gm[e]);
-            }
-        }
+        if (live) load_run<true>(a.pi, a.mu, lp, lm, ((uint32_t)t * (uint32_t)B + (uint32_t)b0) * A, n, A, S, lane);
         __syncthreads();  // the rows are in LDS (a wave reads its own rows only; the round count is uniform)
         if (mine) {
             const float* __restrict__ zp = lp + (uint32_t)lane * S;
@@ -277,7 +173,8 @@ __global__ __launch_bounds__(64 * kWaves) void offpolicy_diag_kernel(DiagArgs a)
         __syncthreads();  // the rows are read: the next round may overwrite them
     }
 
-    // the four waves' sums through LDS, in a fixed order: first the per-column ones, lane = column
+    // the four waves' sums through LDS, in a fixed order: first the per-column ones, lane = column (no
+    // wave reduction, so not block_sums)
     double* const red = (double*)dsm;
 #pragma unroll
     for (int k = 0; k < C_COUNT; ++k) red[(w * C_COUNT + k) * kCols + lane] = col[k];
@@ -290,9 +187,11 @@ __global__ __launch_bounds__(64 * kWaves) void offpolicy_diag_kernel(DiagArgs a)
         a.colp[((size_t)k * a.slices + s) * a.bpad + b0 + ln] = sum;  // columns >= B of the last tile: 0
     }
     __syncthreads();
+    // the other sums: over the wave, then thread i combines quantity i over the waves. Not block_sums:
+    // two entries are extremes, and only the S_COUNT threads that write a partial read red
 #pragma unroll
     for (int i = 0; i < S_COUNT; ++i) {
-        const double x = wave_reduce(op_of(i), acc[i], lane);
+        const double x = wave_reduce_op(op_of(i), acc[i], lane);
         if (lane == 0) red[w * S_COUNT + i] = x;
     }
     __syncthreads();
@@ -354,11 +253,11 @@ __global__ __launch_bounds__(kFinalThreads) void offpolicy_diag_finalize_kernel(
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const double x = wave_reduce(i < C_COUNT ? OP_SUM : op_of(i - C_COUNT), v[i], lane);
+        const double x = wave_reduce_op(i < C_COUNT ? OP_SUM : op_of(i - C_COUNT), v[i], lane);
         if (lane == 0) red[w * NV + i] = x;
     }
     __syncthreads();
-    if (tid < NV) {  // quantity tid over the waves, ascending
+    if (tid < NV) {  // quantity tid over the waves, ascending (not block_sums, as in the kernel above)
         double x = red[tid];
         for (int w2 = 1; w2 < NWV; ++w2) {
             x = combine(tid < C_COUNT ? OP_SUM : op_of(tid - C_COUNT), x, red[w2 * NV + tid]);
@@ -405,16 +304,9 @@ __global__ __launch_bounds__(kFinalThreads) void offpolicy_diag_finalize_kernel(
 
 // ------------------------------------------------------------------ the launcher
 int diag_plan(int T, int B, int A, DiagPlan* out) {
-    FI_REQUIRE(T >= 1 && B >= 1, "offpolicy_diag: T = " + std::to_string(T) + ", B = " + std::to_string(B) + " must be >= 1");
-    FI_REQUIRE(A >= 2 && A <= 64, "offpolicy_diag: A = " + std::to_string(A) + " outside 2 .. 64");
-    FI_REQUIRE((uint64_t)T * (uint64_t)B * (uint64_t)A < (1ull << 31),
-               "offpolicy_diag: T * B * A = " + std::to_string((uint64_t)T * (uint64_t)B * (uint64_t)A) + " passes 2^31 - 1");
-    const int ct = (B + kCols - 1) / kCols;
-    const int want = (kTargetWgs + ct - 1) / ct, most = (T + kWaves - 1) / kWaves;  // a slice holds a round at least
-    const int s0 = want < most ? want : most;
-    int len = (T + s0 - 1) / s0;
-    len = (len + kWaves - 1) / kWaves * kWaves;
-    *out = DiagPlan{ct, (T + len - 1) / len, len};
+    TilePlan p{};
+    FI_TRY(tile_plan("offpolicy_diag", T, B, A, &p));
+    *out = DiagPlan{p.ct, p.slices, p.slice_len};
     return FI_OK;
 }
 
@@ -454,16 +346,9 @@ int offpolicy_diag_launch(int T, int B, int A, const float* pi, const float* mu,
     a.rho_bar = hp.rho_bar, a.c_bar = hp.c_bar, a.pg_rho_bar = hp.pg_rho_bar;
     // the waves' padded rows, and behind the rounds the reductions' scratch (6 KiB, what A = 2 takes)
     const size_t lds = (size_t)kWaves * 2 * kCols * (A | 1) * sizeof(float);
-    if (lds > 64 * 1024) {  // A > 30: above the default limit of dynamic LDS; raised once per device
+    if (lds > 64 * 1024) {  // A > 30: above the default limit of dynamic LDS
         static std::atomic<uint64_t> raised{0};
-        int dev = 0;
-        FI_HIP_CHECK(hipGetDevice(&dev));
-        const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;
-        if (!bit || !(raised.load(std::memory_order_acquire) & bit)) {
-            FI_HIP_CHECK(hipFuncSetAttribute((const void*)offpolicy_diag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)((size_t)kWaves * 2 * kCols * 65 * sizeof(float))));
-            raised.fetch_or(bit, std::memory_order_acq_rel);
-        }
+        FI_TRY(raise_lds((const void*)offpolicy_diag_kernel, raised, (size_t)kWaves * 2 * kCols * 65 * sizeof(float)));
     }
     hipLaunchKernelGGL(offpolicy_diag_kernel, dim3((unsigned)(a.ct * a.slices)), dim3(64 * kWaves), lds, stream, a);
     FI_HIP_CHECK(hipGetLastError());

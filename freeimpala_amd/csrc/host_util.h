@@ -1,13 +1,15 @@
 // host_util.h -- the host-side plumbing the handles of libfi_learner.so share: device allocations,
 // the checks of a caller's device pointers, the exception boundary of a C entry point, the device of
-// a create call and the tail of a step that took its batch. Internal, header-only (inline functions
-// and templates), so any translation unit uses it without depending on another one: learner.cpp
-// still names nothing of actor.hip, ring.hip or the others. A second copy of host plumbing goes here.
+// a create call, the dynamic-LDS limit of a kernel and the tail of a step that took its batch.
+// Internal, header-only (inline functions and templates), so any translation unit uses it without
+// depending on another one: learner.cpp still names nothing of actor.hip, ring.hip or the others. A
+// second copy of host plumbing goes here.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <exception>
 #include <string>
 
@@ -36,6 +38,21 @@ inline int dev_grow(T** p, int* cap, int need, const std::string& what) {
     *cap = 0;
     FI_TRY(dev_alloc((void**)p, sizeof(T) * (size_t)need, what));
     *cap = need;
+    return FI_OK;
+}
+
+// ---------------------------------------------------------------- dynamic LDS above 64 KB
+// Kernel `fn` takes up to `most` bytes of dynamic LDS, more than the default limit: the limit is
+// raised once per device. `raised` is the caller's flag for that kernel, a bit per device id (handles
+// on different devices launch from their own threads).
+inline int raise_lds(const void* fn, std::atomic<uint64_t>& raised, size_t most) {
+    int dev = 0;
+    FI_HIP_CHECK(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;
+    if (!bit || !(raised.load(std::memory_order_acquire) & bit)) {
+        FI_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+        raised.fetch_or(bit, std::memory_order_acq_rel);
+    }
     return FI_OK;
 }
 

@@ -2,11 +2,10 @@
 // the rule stands): the kernels that take the place of the V-trace launch of a step, and every
 // fi_surrogate_* entry point.
 //
-//   surrogate_rows_kernel   a stream over (t, b), diag.hip's read pattern: workgroup (c, s) owns the 64
+//   surrogate_rows_kernel   a stream over (t, b), row_stream.h's pattern: workgroup (c, s) owns the 64
 //                           columns of tile c and the time steps of slice s, its four waves the steps
-//                           t .. t + 3 of a round, lane = column. The pi and mu rows of one (t, tile) are
-//                           one contiguous run: read 16 bytes per lane and access into padded LDS rows
-//                           (stride A | 1 floats: no bank conflicts), then one lane per row. Writes
+//                           t .. t + 3 of a round, lane = column; the pi and mu rows of one (t, tile)
+//                           arrive in padded LDS rows (load_run<true>), then one lane per row. Writes
 //                           d = rho^ (r + g V' - V), k = g c and log rho per row; counts bad actions.
 //   surrogate_scan_kernel   acc_t = d_t + k_t acc_{t+1} down each column, one lane per column, one wave
 //                           per workgroup (64 workgroups at B = 4096, spread over the CUs). The five loads
@@ -36,19 +35,13 @@
 #include "fi_surrogate.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "row_stream.h"  // kCols, kWaves, load_run, store_run, wave_reduce, block_sums, tile_plan
 
 namespace fi {
 
 namespace {
-constexpr int kCols = 64;          // columns per workgroup: lane = column
-constexpr int kWaves = 4;          // waves per workgroup of the two streams: one time step each per round
-constexpr int kTargetWgs = 768;    // three workgroups per CU at B = 4096: the slices of T fill the chip
-constexpr int kPiecesPerLane = 5;  // 16-byte pieces a lane has in flight per tensor (A = 18: 4.5 per lane and run)
-constexpr int kAhead = 8;          // time steps of the scan whose loads are in flight ahead of the chain
+constexpr int kAhead = 8;  // time steps of the scan whose loads are in flight ahead of the chain
 constexpr int kStatThreads = 256;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct StatsBlock {
     uint64_t rows, rows_clipped;
@@ -82,67 +75,6 @@ struct SurArgs {
     uint32_t normalize;
 };
 
-// Wave-wide sum of a double in VALU cross-lane moves (diag.hip's wave_reduce): rotations 8, 4, 2, 1
-// inside each 16-lane row by DPP, then the row pairs and halves by v_permlane16_swap /
-// v_permlane32_swap. The order is fixed; every lane ends with the result.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)u, CTRL, 0xf, 0xf, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-template <int S>
-__device__ __forceinline__ double xor_d(double v, int lane) {  // v of lane ^ S, S = 16 or 32
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    unsigned rlo, rhi;
-    if constexpr (S == 16) {
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        rlo = (lane & 16) ? a[0] : a[1];
-        rhi = (lane & 16) ? b[0] : b[1];
-    } else {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        rlo = (lane & 32) ? a[0] : a[1];
-        rhi = (lane & 32) ? b[0] : b[1];
-    }
-    return __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
-}
-__device__ __forceinline__ double wave_reduce(double v, int lane) {
-    v += dpp_d<0x128>(v);  // row_ror:8
-    v += dpp_d<0x124>(v);  // row_ror:4
-    v += dpp_d<0x122>(v);  // row_ror:2
-    v += dpp_d<0x121>(v);  // row_ror:1
-    v += xor_d<16>(v, lane);
-    v += xor_d<32>(v, lane);
-    return v;
-}
-
-// N sums of a workgroup of NW waves through LDS (red: NW * N doubles), the waves added in ascending
-// order; every thread gets the results. A barrier stands in front of the writes, so red may have been
-// read just before.
-template <int N, int NW>
-__device__ __forceinline__ void block_sums(double (&v)[N], double* red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = wave_reduce(v[i], lane);
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) red[w * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = red[i];
-#pragma unroll
-        for (int w2 = 1; w2 < NW; ++w2) s += red[w2 * N + i];
-        v[i] = s;
-    }
-}
-
 // m and s of A from the scan's partials: thread i adds the partials i, i + 256, ... in ascending order,
 // then block_sums. The loss kernel's workgroups and the stats kernel run this same sequence on the same
 // numbers, so they hold the same bits. n = 1 gives s = 0 exactly: S2 / 1 and (S1 / 1)^2 are one product.
@@ -160,90 +92,6 @@ __device__ __forceinline__ void moments(const SurArgs& a, double* red, double& m
     s = sqrt(var > 0.0 ? var : (var == var ? 0.0 : var));  // NaN stays NaN
 }
 
-// The run of nb * A floats of one (t, tile) from global memory into the wave's padded LDS rows, 16
-// bytes per lane and access, consecutive lanes consecutive pieces; a head and a tail of up to 3 floats
-// where the run does not start or end on a 16-byte boundary. g0 < 2^31 (the launcher's check).
-template <bool kMu>
-__device__ __forceinline__ void load_run(const float* __restrict__ pi, const float* __restrict__ mu, float* __restrict__ lp,
-                                         float* __restrict__ lm, uint32_t g0, uint32_t n, uint32_t A, uint32_t S, int lane) {
-    const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
-    const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
-    const float* __restrict__ gp = pi + g0;
-    const float* __restrict__ gm = mu + g0;
-    const f32x4* __restrict__ gp4 = (const f32x4*)(gp + head);  // 16-byte aligned: (g0 + head) % 4 == 0
-    const f32x4* __restrict__ gm4 = (const f32x4*)(gm + head);
-    for (uint32_t k0 = 0; k0 < nbody; k0 += 64u * kPiecesPerLane) {
-        f32x4 vp[kPiecesPerLane], vm[kPiecesPerLane];
-#pragma unroll
-        for (int u = 0; u < kPiecesPerLane; ++u) {
-            const uint32_t p = k0 + 64u * u + lane;
-            if (p < nbody) {
-                vp[u] = __builtin_nontemporal_load(gp4 + p);
-                if (kMu) vm[u] = __builtin_nontemporal_load(gm4 + p);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kPiecesPerLane; ++u) {
-            const uint32_t p = k0 + 64u * u + lane;
-            if (p < nbody) {
-                const uint32_t e = head + 4u * p;
-                uint32_t r = e / A, cc = e - r * A;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    lp[r * S + cc] = vp[u][j];
-                    if (kMu) lm[r * S + cc] = vm[u][j];
-                    if (++cc == A) {
-                        cc = 0u;
-                        ++r;
-                    }
-                }
-            }
-        }
-    }
-    if ((uint32_t)lane < head) {
-        const uint32_t r = (uint32_t)lane / A, cc = (uint32_t)lane - r * A;
-        lp[r * S + cc] = gp[lane];
-        if (kMu) lm[r * S + cc] = gm[lane];
-    }
-    if ((uint32_t)lane < tail) {
-        const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
-        lp[r * S + cc] = gp[e];
-        if (kMu) lm[r * S + cc] = gm[e];
-    }
-}
-
-// the reverse: the wave's padded LDS rows leave as the run's 16-byte pieces
-__device__ __forceinline__ void store_run(float* __restrict__ out, const float* __restrict__ lp, uint32_t g0, uint32_t n,
-                                          uint32_t A, uint32_t S, int lane) {
-    const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
-    const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
-    float* __restrict__ go = out + g0;
-    f32x4* __restrict__ go4 = (f32x4*)(go + head);
-    for (uint32_t p = lane; p < nbody; p += 64u) {
-        const uint32_t e = head + 4u * p;
-        uint32_t r = e / A, cc = e - r * A;
-        f32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[j] = lp[r * S + cc];
-            if (++cc == A) {
-                cc = 0u;
-                ++r;
-            }
-        }
-        go4[p] = v;
-    }
-    if ((uint32_t)lane < head) {
-        const uint32_t r = (uint32_t)lane / A, cc = (uint32_t)lane - r * A;
-        go[lane] = lp[r * S + cc];
-    }
-    if ((uint32_t)lane < tail) {
-        const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
-        go[e] = lp[r * S + cc];
-    }
-}
-
-constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 }  // namespace
 
 __global__ __launch_bounds__(64 * kWaves) void surrogate_rows_kernel(SurArgs a) {
@@ -470,24 +318,6 @@ __global__ __launch_bounds__(kStatThreads) void surrogate_stats_kernel(SurArgs a
 
 // ------------------------------------------------------------------ the launcher
 namespace {
-struct Plan {
-    int ct, slices, slice_len, nscan;
-};
-
-int plan_of(int T, int B, int A, Plan* out) {
-    FI_REQUIRE(T >= 1 && B >= 1, "surrogate: T = " + std::to_string(T) + ", B = " + std::to_string(B) + " must be >= 1");
-    FI_REQUIRE(A >= 2 && A <= 64, "surrogate: A = " + std::to_string(A) + " outside 2 .. 64");
-    FI_REQUIRE((uint64_t)T * (uint64_t)B * (uint64_t)A < (1ull << 31),
-               "surrogate: T * B * A = " + std::to_string((uint64_t)T * (uint64_t)B * (uint64_t)A) + " passes 2^31 - 1");
-    const int ct = (B + kCols - 1) / kCols;
-    const int want = (kTargetWgs + ct - 1) / ct, most = (T + kWaves - 1) / kWaves;  // a slice holds a round at least
-    const int s0 = want < most ? want : most;
-    int len = (T + s0 - 1) / s0;
-    len = (len + kWaves - 1) / kWaves * kWaves;
-    *out = Plan{ct, (T + len - 1) / len, len, ct};
-    return FI_OK;
-}
-
 size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace: d | k | log rho (T * B floats each) | moment partials | pivot | loss partials | clipped
@@ -495,30 +325,17 @@ size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Layout {
     size_t row, mom, pivot, part, clipped, bad, total;
 };
-Layout layout_of(int T, int B, const Plan& p) {
+Layout layout_of(int T, int B, const TilePlan& p) {
     Layout l{};
     const size_t nblk = (size_t)p.ct * p.slices;
     l.row = pad256((size_t)T * B * sizeof(float));
     l.mom = 3 * l.row;
-    l.pivot = l.mom + pad256((size_t)p.nscan * 2 * sizeof(double));
+    l.pivot = l.mom + pad256((size_t)p.ct * 2 * sizeof(double));
     l.part = l.pivot + 256;
     l.clipped = l.part + pad256(nblk * 3 * sizeof(double));
     l.bad = l.clipped + pad256(nblk * sizeof(unsigned long long));
     l.total = l.bad + 256;
     return l;
-}
-
-// more than 64 KB of dynamic LDS (A > 30 for the rows kernel, A = 63, 64 for the loss kernel): the
-// kernel's limit is raised once per device (a bit per device id)
-int raise_lds(const void* fn, std::atomic<uint64_t>& raised, size_t most) {
-    int dev = 0;
-    FI_HIP_CHECK(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;
-    if (!bit || !(raised.load(std::memory_order_acquire) & bit)) {
-        FI_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-        raised.fetch_or(bit, std::memory_order_acq_rel);
-    }
-    return FI_OK;
 }
 
 int check_params(const std::string& who, const fi_surrogate_params* p) {
@@ -532,13 +349,13 @@ int check_params(const std::string& who, const fi_surrogate_params* p) {
 }  // namespace
 
 size_t surrogate_workspace_bytes(int T, int B, int A) {
-    Plan p{};
-    return plan_of(T, B, A, &p) == FI_OK ? layout_of(T, B, p).total : 0;
+    TilePlan p{};
+    return tile_plan("surrogate", T, B, A, &p) == FI_OK ? layout_of(T, B, p).total : 0;
 }
 
 int surrogate_loss_blocks(int T, int B, int A) {
-    Plan p{};
-    return plan_of(T, B, A, &p) == FI_OK ? p.ct * p.slices : 0;
+    TilePlan p{};
+    return tile_plan("surrogate", T, B, A, &p) == FI_OK ? p.ct * p.slices : 0;
 }
 
 int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
@@ -546,8 +363,8 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
                      float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
                      int* bad, hipStream_t stream, KernelTagger* tg, const double** partials, int* nblk_out) {
     FI_REQUIRE(pi && mu && act && rew && disc && val && vs && adv && dlog && dval && ws, "surrogate: null argument");
-    Plan p{};
-    FI_TRY(plan_of(T, B, A, &p));
+    TilePlan p{};
+    FI_TRY(tile_plan("surrogate", T, B, A, &p));
     FI_REQUIRE((uintptr_t)pi % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)dlog % 16 == 0,
                "surrogate: pi, mu and dlogits must be 16-byte aligned (16 bytes move per lane and access)");
     FI_REQUIRE((uintptr_t)act % 4 == 0 && (uintptr_t)rew % 4 == 0 && (uintptr_t)disc % 4 == 0 && (uintptr_t)val % 4 == 0 &&
@@ -562,7 +379,7 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
     char* w = (char*)ws;
     SurArgs a{};
     a.T = T, a.B = B, a.A = A;
-    a.ct = p.ct, a.slices = p.slices, a.slice_len = p.slice_len, a.nscan = p.nscan;
+    a.ct = p.ct, a.slices = p.slices, a.slice_len = p.slice_len, a.nscan = p.ct;  // the scan: a workgroup per column tile
     a.pi = pi, a.mu = mu, a.act = act, a.rew = rew, a.disc = disc, a.val = val;
     a.vs = vs, a.adv = adv, a.dlog = dlog, a.dval = dval;
     a.d = (float*)w, a.k = (float*)(w + lay.row), a.lr = (float*)(w + 2 * lay.row);
@@ -577,6 +394,7 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
     }
     const unsigned nblk = (unsigned)(p.ct * p.slices);
     const size_t row_bytes = (size_t)kWaves * kCols * (A | 1) * sizeof(float), row_most = (size_t)kWaves * kCols * 65 * 4;
+    // more than 64 KB of dynamic LDS: A > 30 for the rows kernel, A = 63, 64 for the loss kernel
     if (2 * row_bytes > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
         FI_TRY(raise_lds((const void*)surrogate_rows_kernel, raised, 2 * row_most));
@@ -592,7 +410,7 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
     }
     {
         TagScope t(tg, "surrogate_scan");
-        hipLaunchKernelGGL(surrogate_scan_kernel, dim3((unsigned)p.nscan), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL(surrogate_scan_kernel, dim3((unsigned)a.nscan), dim3(64), 0, stream, a);
         FI_HIP_CHECK(hipGetLastError());
     }
     {

@@ -29,6 +29,7 @@
 // Kernel 2 (vtrace_column_kernel): one lane per column, serial over t; any A <= 64, any B.
 #include "fi_common.h"
 #include "kernels.h"
+#include "row_stream.h"  // f32x2, f32x4, L2E, LN2, wave_reduce
 
 #include <atomic>
 #include <algorithm>
@@ -46,9 +47,6 @@ namespace fi {
 #else
 #define VT_ST(v, p) (*(p) = (v))
 #endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // max of three through v_max3_f32 directly: fmaxf() under the kernels' IEEE mode makes hipcc
 // quiet every LDS-loaded operand first (one v_max_f32 x, x, x each), doubling the row-max cost
@@ -78,46 +76,15 @@ struct VtArgs {
 
 constexpr size_t kSinkFloats = 2048;
 
-// wave-wide double sum in VALU cross-lane moves (no ds_bpermute round trips in the
-// workgroup's tail): rotations 8, 4, 2, 1 inside each 16-lane row by DPP, then the row pairs
-// and halves by gfx950's v_permlane16_swap / v_permlane32_swap. The summation order is
-// fixed, so the result is deterministic; lane 0 holds the total the callers use.
-template <int CTRL>
-__device__ __forceinline__ double vt_dpp_d(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)u, CTRL, 0xf, 0xf, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-template <int S>
-__device__ __forceinline__ double vt_xor_d(double v, int lane) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    unsigned rlo, rhi;
-    if constexpr (S == 16) {
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        rlo = (lane & 16) ? a[0] : a[1];
-        rhi = (lane & 16) ? b[0] : b[1];
-    } else {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        rlo = (lane & 32) ? a[0] : a[1];
-        rhi = (lane & 32) ? b[0] : b[1];
-    }
-    return __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
-}
+// wave-wide double sum: row_stream.h's reduction (lane 0 holds the total the callers use)
 __device__ __forceinline__ double vt_wave_sum(double v) {
     const int lane = threadIdx.x & 63;
-    v += vt_dpp_d<0x128>(v);  // row_ror:8
-    v += vt_dpp_d<0x124>(v);  // row_ror:4
-    v += vt_dpp_d<0x122>(v);  // row_ror:2
-    v += vt_dpp_d<0x121>(v);  // row_ror:1
-    v += vt_xor_d<16>(v, lane);
-    v += vt_xor_d<32>(v, lane);
-    return v;
+    return wave_reduce(v, lane);
 }
 
+// The three loss sums of a workgroup: thread i adds quantity i over the waves. Not row_stream.h's
+// block_sums: the sum starts from 0.0 (a -0.0 comes out as +0.0), the wave count is blockDim's, no
+// barrier stands in front of the writes and only three threads read red.
 __device__ __forceinline__ void block_reduce3(double pg, double base, double ent, double* red,
                                               double* out) {
     pg = vt_wave_sum(pg);
@@ -362,7 +329,6 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
 
         // packed-fp32 softmax statistics: e_i = 2^(z_i log2e - max log2e) (one v_pk_fma +
         // one v_exp_f32 per logit), pi_i = e_i / sum e, H = sum pi log pi = (sum e z)/sum e - lse
-        constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
         f32x2 zp2[A / 2], zm2[A / 2];
 #pragma unroll
         for (int i = 0; i < A / 2; ++i) {
@@ -599,7 +565,6 @@ __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
     float* tot = (float*)(vsm + 2 * SB);  // [NW][NC][2] wave totals
     const VtRsrc rs = vt_rsrc(a);
     const fi_vtrace_hparams hp = a.hp;
-    constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
     float pg = 0.f, base = 0.f, ent = 0.f;
     float* const sink = a.sink + tid;
     int k = 0;
@@ -861,7 +826,6 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
         at = at < 0 ? 0 : (at >= A ? A - 1 : at);
 
         // softmax statistics of the lane's own row (as kernel 1)
-        constexpr float L2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
         float* const zpi = (float*)(sl + (size_t)tt * L::ROWB) + c * A;
         const float* const zmu = (const float*)(sl + L::tile_bytes(T) + (size_t)tt * L::ROWB) + c * A;
         f32x2 zp2[A / 2], zm2[A / 2];

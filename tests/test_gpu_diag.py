@@ -21,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(1, 1, 3), (1, 8, 2), (5, 24, 18), (33, 72, 18), (7, 65, 64), (20, 136, 6)]
+SHAPES = [(1, 1, 3), (1, 8, 2), (5, 24, 18), (33, 72, 18), (7, 65, 64), (20, 136, 6), (3, 5, 3), (6, 67, 3)]
 BARS = (1.3, 0.9, 2.1)  # rho_bar, c_bar, pg_rho_bar: away from the rho = 1 cluster of saturated rows
 G = 64                  # guard bytes on both sides of every output
 TOL = 1e-5
@@ -156,6 +156,25 @@ def shape_run(shape):
 
 
 # ------------------------------------------------------------------ 1. the kernels alone
+def run_pieces(shapes):
+    """(head, n - head) of the run of every (t, column tile) of every shape: the run starts at float
+    g0 = (t B + 64 c) A and has n = nb A floats; its head are the floats in front of the first 16-byte boundary."""
+    for T, B, A in shapes:
+        for t in range(T):
+            for b0 in range(0, B, 64):
+                g0, n = (t * B + b0) * A, min(64, B - b0) * A
+                head = min(-g0 % 4, n)
+                yield head, n - head
+
+
+def assert_runs_cover_the_pieces(shapes):
+    pieces = set(run_pieces(shapes))
+    for h in (1, 2, 3):
+        assert any(head == h for head, _ in pieces), f"a run that starts {h} floats in front of a 16-byte boundary"
+    assert any(head and rest >= 4 and rest % 4 for head, rest in pieces), "a run with a head, 16-byte pieces and a tail"
+    assert any(rest < 4 for _, rest in pieces), "a run without a 16-byte piece"
+
+
 def test_shapes_cover_the_plan():
     from freeimpala_amd import diag
     plans = {s: diag.plan(*s) for s in SHAPES}
@@ -164,8 +183,7 @@ def test_shapes_cover_the_plan():
     assert any(p[0] > 1 for p in plans.values()), "more than one column tile"
     assert any(p[1] > 1 for p in plans.values()), "more than one time slice"
     assert any(p[0] > 1 and p[1] > 1 for p in plans.values())
-    # odd B * A and runs that start off a 16-byte boundary: a head and a tail piece
-    assert any((s[1] * s[2]) % 4 != 0 for s in SHAPES) and any(s[2] % 4 != 0 for s in SHAPES)
+    assert_runs_cover_the_pieces(SHAPES)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))

@@ -19,7 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_diag import BARS, TOL as DIAG_TOL, make_learner
+from test_gpu_diag import BARS, TOL as DIAG_TOL, assert_runs_cover_the_pieces, make_learner
 from test_gpu_popart import kernel_tags, stat_bars
 from test_gpu_prio import ETA, bar as prio_bar
 from test_gpu_ring import Guarded, make_entries, spaced
@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIG = (9, 200, 5)  # 4 column tiles x 3 slices in the rows and loss kernels, 4 workgroups in the scan
-SHAPES = [(1, 1, 3), (1, 8, 2), (5, 24, 18), (33, 72, 18), (7, 65, 64), (20, 136, 6), BIG]
+SHAPES = [(1, 1, 3), (1, 8, 2), (5, 24, 18), (33, 72, 18), (7, 65, 64), (20, 136, 6), BIG, (3, 5, 3), (6, 67, 3)]
 SEEDS = {(20, 136, 6): 1}  # 1000 T + 10 B + A gives a row within 1e-4 of 1 + clip there
 CLIP = 0.2
 TAGS = ["surrogate_rows", "surrogate_scan", "surrogate_loss", "surrogate_stats"]
@@ -149,8 +149,8 @@ def test_shapes_cover_the_grids():
     assert any(blocks[s][0] > blocks[s][1] for s in SHAPES), "more than one time slice"
     assert any(s[0] % 4 != 0 and s[0] > 4 for s in SHAPES), "a last round with idle waves"
     assert any(s[0] > 8 and s[0] % 8 != 0 for s in SHAPES), "a scan whose last run of eight steps is partial"
-    # odd B * A and runs that start off a 16-byte boundary: a head and a tail piece; A = 64: the raised LDS limit
-    assert any((s[1] * s[2]) % 4 != 0 for s in SHAPES) and any(s[2] % 4 != 0 for s in SHAPES) and any(s[2] == 64 for s in SHAPES)
+    assert_runs_cover_the_pieces(SHAPES)
+    assert any(s[2] == 64 for s in SHAPES), "A = 64: the raised LDS limit"
 
 
 @pytest.mark.parametrize("normalize", [False, True], ids=["plain", "normalized"])
