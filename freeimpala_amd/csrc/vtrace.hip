@@ -518,7 +518,12 @@ __device__ __forceinline__ void vt_str_issue(const VtRsrc& rs, uint32_t slot_lds
     const int per_wave = (NPc + L::NW - 1) / L::NW;
     for (int i = 0; i < per_wave; ++i) {
         int j = w + L::NW * i;
-        if (j >= NPc) j = w;  // pad the wave's count: a duplicate of its first piece (same bytes, same place)
+        // pad the wave's count with a duplicate of a piece that exists (same bytes, same place): its
+        // own first one, or, where a short sequence has fewer pieces than waves, piece w - NPc --
+        // never a piece past the slot, which would land in the other slot or in tot. pieces(T) >= 6
+        // for every T >= 1 (2 logits + 3 scalar + 1 value piece), so 0 <= w - NPc < NW - 6 <= NPc
+        static_assert(L::pieces(1) == 6 && L::NW - 6 <= 6, "pad piece w - NPc must exist");
+        if (j >= NPc) j = w < NPc ? w : w - NPc;
         const int q0 = 16 * lane;
         if (j < 2 * LP) {  // pi | mu
             const int jj = j < LP ? j : j - LP;

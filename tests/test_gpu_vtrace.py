@@ -3,75 +3,16 @@
 Bar (BASELINE.json north_star): vs, pg_adv, dlogits, dvalue elementwise
 |d| <= 1e-5 * max(1, |ref|); loss scalars relative 1e-5 (fp32 kernels vs fp64 oracle).
 """
-import ctypes as C
 import glob
 import os
 
 import numpy as np
 import pytest
 
+from vtrace_cases import HP_KEYS, TOL, _close, compare, rand_case, run_vtrace, str_shape_ok  # noqa: F401 (re-exported)
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-HP_KEYS = ["rho_bar", "c_bar", "pg_rho_bar", "lambda_", "baseline_cost", "entropy_cost"]
-TOL = 1e-5
-
-
-def _close(a, b, tol=TOL, what=""):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    err = np.abs(a - b) / np.maximum(1.0, np.abs(b))
-    assert np.isfinite(a).all(), what
-    assert err.max() <= tol, f"{what}: max rel err {err.max():.3e} at {np.unravel_index(err.argmax(), err.shape)}"
-
-
-def run_vtrace(pi, mu, act, rew, disc, val, variant=0, **hp):
-    from freeimpala_amd import _abi, hip
-    T, B, A = pi.shape
-    h = dict(rho_bar=1.0, c_bar=1.0, pg_rho_bar=1.0, lambda_=1.0, baseline_cost=0.5,
-             entropy_cost=0.01)
-    h.update(hp)
-    H = _abi.VtraceHparams(**h)
-    bufs = {k: hip.DeviceBuffer.from_array(np.ascontiguousarray(v, dt))
-            for k, v, dt in [("pi", pi, np.float32), ("mu", mu, np.float32),
-                             ("act", act, np.int32), ("rew", rew, np.float32),
-                             ("disc", disc, np.float32), ("val", val, np.float32)]}
-    vs = hip.DeviceBuffer(T * B * 4)
-    adv = hip.DeviceBuffer(T * B * 4)
-    dl = hip.DeviceBuffer(T * B * A * 4)
-    dv = hip.DeviceBuffer((T + 1) * B * 4)
-    loss = hip.DeviceBuffer(3 * 8)
-    wsb = _abi.lib().fi_vtrace_workspace_bytes(T, B, A)
-    ws = hip.DeviceBuffer(wsb)
-    ws.zero()
-    rc = _abi.lib().fi_vtrace_loss_fp32_variant(
-        variant, T, B, A, bufs["pi"].ptr, bufs["mu"].ptr, bufs["act"].ptr, bufs["rew"].ptr,
-        bufs["disc"].ptr, bufs["val"].ptr, C.byref(H), vs.ptr, adv.ptr, dl.ptr, dv.ptr, loss.ptr,
-        ws.ptr, wsb, None)
-    _abi.check(rc, "fi_vtrace_loss_fp32_variant")
-    hip.synchronize()
-    return dict(vs=vs.download(np.float32, (T, B)), pg_adv=adv.download(np.float32, (T, B)),
-                dlogits=dl.download(np.float32, (T, B, A)),
-                dvalue=dv.download(np.float32, (T + 1, B)),
-                losses=loss.download(np.float64, (3,)))
-
-
-def compare(out, ref, tol=TOL):
-    for k in ("vs", "pg_adv", "dlogits", "dvalue"):
-        _close(out[k], ref[k], tol, k)
-    for i in range(3):
-        r = ref["losses"][i]
-        assert abs(out["losses"][i] - r) <= tol * max(1.0, abs(r)), (i, out["losses"], ref["losses"])
-
-
-def rand_case(seed, T, B, A, scale=1.0, done_p=0.02, gamma=0.99):
-    rs = np.random.RandomState(seed)
-    pi = (rs.randn(T, B, A) * scale).astype(np.float32)
-    mu = (rs.randn(T, B, A) * scale).astype(np.float32)
-    act = rs.randint(0, A, (T, B)).astype(np.int32)
-    rew = rs.choice([-1.0, 0.0, 1.0], (T, B)).astype(np.float32)
-    disc = np.where(rs.rand(T, B) < done_p, 0.0, gamma).astype(np.float32)
-    val = rs.randn(T + 1, B).astype(np.float32)
-    return pi, mu, act, rew, disc, val
 
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "vtrace_*.npz"))))
@@ -82,13 +23,6 @@ def test_vtrace_golden(path):
     compare(out, {k: z[k] for k in ("vs", "pg_adv", "dlogits", "dvalue", "losses")})
 
 
-def str_shape_ok(T, A):
-    """variant 4's limits (vtrace.hip str_supported): T <= 127, T * A <= 2048 dlogits pieces, the
-    two whole-sequence slots within 160 KB of LDS."""
-    lds = 2 * 1024 * (2 * -(-T * 16 * A // 1024) + 3 * -(-T * 16 // 1024) + -(-(T + 1) * 16 // 1024)) + 256
-    return T <= 127 and T * A <= 2048 and lds <= 160 * 1024
-
-
 @pytest.mark.parametrize("T,B,A", [(1, 16, 18), (16, 16, 18), (17, 32, 18), (33, 48, 4),
                                    (100, 64, 2), (100, 32, 20), (50, 16, 6), (3, 16, 18),
                                    (100, 256, 18), (128, 64, 18), (127, 16, 18), (65, 24, 18)])
@@ -96,7 +30,7 @@ def str_shape_ok(T, A):
 def test_vtrace_kernels_vs_oracle(orc, T, B, A, variant):
     if variant == 4 and not str_shape_ok(T, A):
         pytest.skip("the streaming kernel holds a group's whole sequence in LDS and stores at most "
-                    "2,048 dlogits pieces (T <= 113 at A = 18)")
+                    "2,048 dlogits pieces (vtrace.hip str_supported; vtrace_cases.str_shape_ok)")
     case = rand_case(T * 1000 + B + A, T, B, A)
     ref = orc.vtrace_loss(*case)
     out = run_vtrace(*case, variant=variant)
