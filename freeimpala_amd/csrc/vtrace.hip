@@ -27,6 +27,16 @@
 // buffer offsets; vtrace_launch falls back to kernel 2 above that).
 //
 // Kernel 2 (vtrace_column_kernel): one lane per column, serial over t; any A <= 64, any B.
+//
+// Kernels 3 and 4, on request only (variants 3 and 4; both measured slower than kernel 1,
+// DESIGN.md section 5), hold a column group's WHOLE sequence in LDS, so there is no chain of
+// time chunks: vtrace_seq_kernel<A> gives a 256-thread workgroup 2 columns (T <= 128, a DPP
+// prefix scan in reverse-time lane order), vtrace_stream_kernel<A> a 512-thread one 4 columns
+// (T <= 127, the butterfly of kernel 1 by shuffles). Each is described in front of its code.
+//
+// What a (t, b) row computes exists once, in the vt_row_* helpers below the column kernel:
+// kernels 1, 3 and 4 differ in how rows map to lanes, how the data arrives and how the scan
+// crosses lanes and waves, not in the arithmetic.
 #include "fi_common.h"
 #include "kernels.h"
 #include "row_stream.h"  // f32x2, f32x4, L2E, LN2, wave_reduce
@@ -35,18 +45,13 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 
 namespace fi {
 
 #define VT_EXP(x) __expf(x)
-#define VT_LOG(x) __logf(x)
 #define VT_EXP2(x) __builtin_amdgcn_exp2f(x)
 #define VT_LOG2(x) __builtin_amdgcn_logf(x)
-#ifdef FI_VT_NT
-#define VT_ST(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define VT_ST(v, p) (*(p) = (v))
-#endif
 
 // max of three through v_max3_f32 directly: fmaxf() under the kernels' IEEE mode makes hipcc
 // quiet every LDS-loaded operand first (one v_max_f32 x, x, x each), doubling the row-max cost
@@ -165,6 +170,180 @@ __global__ __launch_bounds__(256) void vtrace_column_kernel(VtArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
+// One (t, b) row of the LDS kernels 1, 3 and 4: the thread that owns the row has its pi and mu
+// logits in LDS (zpi, zmu). Small results come back by value and `if (valid)` stays with the
+// caller: with reference parameters for the loss sums, or with the test inside a helper, hipcc
+// schedules kernel 1 differently (profiles/AB_HISTORY.md, "V-trace: one copy of the row math").
+// ------------------------------------------------------------------------------------
+// KEEP_E: the e_i stay in registers from the statistics to the dlogits row (kernels 1 and 3).
+// Kernel 4 runs 512 threads on a tight register budget and computes them a second time
+// instead (vt_row_e), so that it holds no e2 across its barriers.
+template <int A, bool KEEP_E>
+struct VtRow {
+    f32x2 zp2[A / 2];              // the pi logits
+    f32x2 e2[KEEP_E ? A / 2 : 1];  // e_i = 2^(z_i log2e - max log2e)
+    f32x2 nmx;                     // -max log2e, twice
+    int at;                        // the action, clamped to [0, A)
+    float lse, inv, plogp;         // log sum e^z, 1 / sum e, H = sum pi log pi
+    float lpa, ratio;              // log pi(a), pi(a) / mu(a)
+    float rho, cc, pgr;            // the clipped weights: rho, lambda c, pg-rho
+    // what vt_row_load and vt_row_exp hand on to vt_row_weights
+    f32x2 zm2[A / 2];
+    f32x2 sp2, sm2, sz2;
+    float mx, mm, zpa, zma;
+};
+
+// The row's logits and action (*pact; one outside [0, A) is counted in *bad if the row holds a
+// time step, and clamped). Apart from vt_row_exp, so that a kernel can read the row's scalars
+// in between: the LDS reads then issue in the order they always had.
+template <int A, bool KEEP_E>
+__device__ __forceinline__ void vt_row_load(VtRow<A, KEEP_E>& r, const float* zpi, const float* zmu, const int* pact,
+                                            bool valid, int* bad) {
+#pragma unroll
+    for (int i = 0; i < A / 2; ++i) {
+        r.zp2[i] = *(const f32x2*)(zpi + 2 * i);
+        r.zm2[i] = *(const f32x2*)(zmu + 2 * i);
+    }
+    const int at = *pact;
+    if (valid && (unsigned)at >= (unsigned)A) atomicAdd(bad, 1);
+    r.at = at < 0 ? 0 : (at >= A ? A - 1 : at);
+    r.zpa = zpi[r.at];
+    r.zma = zmu[r.at];
+}
+
+// packed-fp32 softmax statistics: e_i = 2^(z_i log2e - max log2e) (one v_pk_fma +
+// one v_exp_f32 per logit), pi_i = e_i / sum e, H = sum pi log pi = (sum e z)/sum e - lse.
+// Up to the seam where kernel 1 issues its middle DMA group: the row maxima and the exponentials.
+template <int A, bool KEEP_E>
+__device__ __forceinline__ void vt_row_exp(VtRow<A, KEEP_E>& r) {
+    float mx = vt_max3(r.zp2[0].x, r.zp2[0].y, r.zp2[0].y), mm = vt_max3(r.zm2[0].x, r.zm2[0].y, r.zm2[0].y);
+#pragma unroll
+    for (int i = 1; i < A / 2; ++i) {
+        mx = vt_max3(mx, r.zp2[i].x, r.zp2[i].y);
+        mm = vt_max3(mm, r.zm2[i].x, r.zm2[i].y);
+    }
+    const f32x2 nmx = {-mx * L2E, -mx * L2E}, nmm = {-mm * L2E, -mm * L2E};
+    f32x2 sp2 = {0.f, 0.f}, sm2 = {0.f, 0.f}, sz2 = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < A / 2; ++i) {
+        const f32x2 ap = r.zp2[i] * L2E + nmx;
+        const f32x2 am = r.zm2[i] * L2E + nmm;
+        const f32x2 e = f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
+        if constexpr (KEEP_E) r.e2[i] = e;
+        sp2 += e;
+        sz2 += e * r.zp2[i];
+        sm2 += f32x2{VT_EXP2(am.x), VT_EXP2(am.y)};
+    }
+    r.mx = mx, r.mm = mm, r.nmx = nmx;
+    r.sp2 = sp2, r.sm2 = sm2, r.sz2 = sz2;
+}
+template <int A, bool KEEP_E>
+__device__ __forceinline__ f32x2 vt_row_e(const VtRow<A, KEEP_E>& r, int i) {
+    if constexpr (KEEP_E) {
+        return r.e2[i];
+    } else {
+        const f32x2 ap = r.zp2[i] * L2E + r.nmx;
+        return f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
+    }
+}
+
+// After the seam: the log-sum-exps, the entropy term, the importance ratio and its three clips.
+template <int A, bool KEEP_E>
+__device__ __forceinline__ void vt_row_weights(VtRow<A, KEEP_E>& r, const fi_vtrace_hparams& hp) {
+    const float sp = r.sp2.x + r.sp2.y, sm = r.sm2.x + r.sm2.y;
+    const float lse = r.mx + VT_LOG2(sp) * LN2, lsem = r.mm + VT_LOG2(sm) * LN2;
+    const float inv = __builtin_amdgcn_rcpf(sp);
+    const float plogp = (r.sz2.x + r.sz2.y) * inv - lse;
+    const float lpa = r.zpa - lse, lma = r.zma - lsem;
+    const float ratio = VT_EXP(lpa - lma);
+    r.lse = lse, r.inv = inv, r.plogp = plogp, r.lpa = lpa, r.ratio = ratio;
+    r.rho = fminf(hp.rho_bar, ratio);
+    r.cc = hp.lambda_ * fminf(hp.c_bar, ratio);
+    r.pgr = fminf(hp.pg_rho_bar, ratio);
+}
+
+// The row's step of the recurrence, acc_t = d + g acc_{t+1}; a row that holds no time step is
+// the identity (0, 1).
+struct VtAffine {
+    float d, g;
+};
+__device__ __forceinline__ VtAffine vt_row_affine(bool valid, float rho, float cc, float rw, float g, float v, float vn) {
+    return VtAffine{valid ? rho * (rw + g * vn - v) : 0.f, valid ? g * cc : 1.f};
+}
+
+// The row's targets once the scan has delivered acc_{t+1} (acc_nx).
+struct VtTargets {
+    float acc, vs_t, adv, dv;
+};
+__device__ __forceinline__ VtTargets vt_row_targets(float d_own, float g_own, float acc_nx, float v, float vn, float rw,
+                                                    float g, float pgr, float baseline_cost) {
+    VtTargets o;
+    o.acc = d_own + g_own * acc_nx;
+    o.vs_t = v + o.acc;
+    const float vs_n = vn + acc_nx;
+    o.adv = pgr * (rw + g * vs_n - v);
+    o.dv = -baseline_cost * o.acc;
+    return o;
+}
+
+// dlogits over the thread's own pi row in LDS:
+//   dz_i = pi_i (adv + ec (log pi_i - H)) - adv [i = a_t] = e_i (alpha + beta z_i) - adv [i = a_t]
+template <int A, bool KEEP_E>
+__device__ __forceinline__ void vt_row_dlogits(const VtRow<A, KEEP_E>& r, float* zpi, float adv, float ec) {
+    const float al = r.inv * (adv - ec * (r.plogp + r.lse)), be = r.inv * ec;
+    const f32x2 al2 = {al, al};
+#pragma unroll
+    for (int i = 0; i < A / 2; ++i) *(f32x2*)(zpi + 2 * i) = vt_row_e(r, i) * (r.zp2[i] * be + al2);
+    zpi[r.at] -= adv;
+}
+
+// the three loss sums of a thread (policy gradient, baseline, entropy) and a row's terms added
+struct VtLoss {
+    float pg, base, ent;
+};
+__device__ __forceinline__ VtLoss vt_row_losses(VtLoss s, float adv, float lpa, float acc, float plogp) {
+    s.pg += -adv * lpa;
+    s.base += 0.5f * acc * acc;
+    s.ent += plogp;
+    return s;
+}
+
+// The exchange with lane ^ S of a scan step. VtXorDpp stays in VALU cross-lane ops (no LDS round
+// trip): S = 8 by DPP row_ror:8 inside each 16-lane row, S = 16 / 32 by gfx950's v_permlane16_swap /
+// v_permlane32_swap. VtXorShfl is a shuffle: any S.
+struct VtXorDpp {
+    template <int S>
+    static __device__ __forceinline__ float get(float v, int lane) {
+        const unsigned u = __float_as_uint(v);
+        if constexpr (S == 8) {
+            return __uint_as_float(__builtin_amdgcn_update_dpp(0u, u, 0x128, 0xf, 0xf, false));
+        } else if constexpr (S == 16) {
+            const auto q = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+            return __uint_as_float((lane & 16) ? q[0] : q[1]);
+        } else {
+            const auto q = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+            return __uint_as_float((lane & 32) ? q[0] : q[1]);
+        }
+    }
+};
+struct VtXorShfl {
+    template <int S>
+    static __device__ __forceinline__ float get(float v, int) { return __shfl_xor(v, S, 64); }
+};
+// One butterfly step of the affine suffix scan over rows S lanes apart: (sd, sg) = the composition
+// of the lane's current row segment, (ed, eg) = the composition of the rows after this one inside
+// it; after the last step (sd, sg) is the wave total in every row
+template <int S, class Exchange>
+__device__ __forceinline__ void vt_scan_step(float& sd, float& sg, float& ed, float& eg, int lane) {
+    const float pd = Exchange::template get<S>(sd, lane), pg = Exchange::template get<S>(sg, lane);
+    const bool later = (lane & S) == 0;  // partner segment holds later rows
+    ed = later ? ed + eg * pd : ed;
+    eg = later ? eg * pg : eg;
+    sd = later ? sd + sg * pd : pd + pg * sd;
+    sg = sg * pg;
+}
+
+// ------------------------------------------------------------------------------------
 // Kernel 1: LDS-staged reverse-time chunks, LDS-DMA double buffer, shuffle scan.
 // Workgroup = 8 batch columns x all T, 256 threads, two workgroups per CU (81,920 B of LDS
 // each) so one workgroup's arithmetic overlaps the other's DMA waits. A chunk is 32
@@ -174,12 +353,9 @@ __global__ __launch_bounds__(256) void vtrace_column_kernel(VtArgs a) {
 // (data landed, wave totals visible). Pieces of the partial (earliest) chunk that hold no
 // valid timestep are not fetched.
 // ------------------------------------------------------------------------------------
-#ifndef FI_VT_NW
-#define FI_VT_NW 4
-#endif
 template <int A>
 struct VtLayout {
-    static constexpr int NW = FI_VT_NW;                // waves per workgroup (8 rows each)
+    static constexpr int NW = 4;                       // waves per workgroup (8 rows each)
     static constexpr int NB = 8;                       // batch columns per workgroup
     static constexpr int TC = 8 * NW;                  // timesteps per chunk
     static constexpr int ROWF = NB * A;                // floats per t-row of a logits tile
@@ -187,23 +363,18 @@ struct VtLayout {
     static constexpr int LOGB = TC * ROWB;             // bytes per logits tile (= 256*NW*A)
     static constexpr int SCB = TC * NB * 4;            // bytes per scalar tile (= 256*NW)
     static constexpr int PT = LOGB / 1024;             // 1-KiB pieces per logits tile
-    static constexpr int MUB = LOGB;
-    static constexpr int TOTB = 0;
     static constexpr int GLOG = 2 * PT / NW;           // logits pieces per wave per chunk
-    static constexpr int SCO = LOGB + MUB;             // scalar tiles' offset in a slot
-    static constexpr int SLOT = SCO + 4 * SCB + TOTB;  // pi | mu | act | rew | disc | val [| tot]
+    static constexpr int SCO = 2 * LOGB;               // scalar tiles' offset in a slot
+    static constexpr int SLOT = SCO + 4 * SCB;         // pi | mu | act | rew | disc | val
     static constexpr int RING = 2;
     static constexpr int TOTAL = RING * SLOT;
     static constexpr int WPS0 = (163840 / TOTAL) * NW / 4;  // waves per SIMD the LDS allows
     static constexpr int WPS = WPS0 < 1 ? 1 : (WPS0 > 8 ? 8 : WPS0);
     static_assert(A % 2 == 0, "fast V-trace kernel needs even A");
-    static_assert((NW == 2 || NW == 4) && LOGB % 1024 == 0 && (2 * PT) % NW == 0 && SCB == 256 * NW, "tiling");
+    static_assert(LOGB % 1024 == 0 && (2 * PT) % NW == 0 && SCB == 256 * NW, "tiling");
     static_assert(TOTAL <= 160 * 1024, "LDS budget");
 };
 
-// queue chunk (rows t0 .. t0+31) into ring slot `slot`; returns the pieces this wave issued
-// (pieces I0 <= i < I1 of this wave's list: logits pieces 0..GLOG-1, then its scalar piece;
-// the list is issued in groups between arithmetic so the TA drains between them)
 struct VtRsrc {  // buffer descriptors of the six input tensors (built once per workgroup)
     fi_i32x4 pi, mu, act, rew, disc, val;
 };
@@ -213,6 +384,9 @@ __device__ __forceinline__ VtRsrc vt_rsrc(const VtArgs& a) {
                   make_rsrc(a.rew, sbytes), make_rsrc(a.disc, sbytes), make_rsrc(a.val, sbytes + a.B * 4)};
 }
 
+// queue chunk (rows t0 .. t0+31) into ring slot `slot`; returns the pieces this wave issued
+// (pieces I0 <= i < I1 of this wave's list: logits pieces 0..GLOG-1, then its scalar piece;
+// the list is issued in groups between arithmetic so the TA drains between them)
 template <int A, int I0, int I1>
 __device__ __forceinline__ int vt_issue_chunk(const VtArgs& a, const VtRsrc& rs, uint32_t lds0, int slot,
                                               int t0, int b0, int w, int lane) {
@@ -235,50 +409,14 @@ __device__ __forceinline__ int vt_issue_chunk(const VtArgs& a, const VtRsrc& rs,
                base + (j < L::PT ? 0 : L::LOGB) + jj * 1024);
         ++n;
     }
-    if (I1 > L::GLOG) {  // scalar tiles (TC rows x 8 columns x 4 B): wave w's piece holds 4/NW of them,
-       // lane -> (tile, row, 16-B half of the row)
-        constexpr int LPT = 16 * L::NW;  // lanes per tile
-        const int s = w * (4 / L::NW) + lane / LPT;
-        const int t = max(t0 + ((lane % LPT) >> 1), 0);
-        // the piece's 4/NW tiles come from up to 4 tensors: one descriptor per tile, lanes select
+    if (I1 > L::GLOG) {  // scalar tiles (TC rows x 8 columns x 4 B): wave w's piece is tile w (act, rew,
+                         // disc, val), lane -> (row, 16-B half of the row)
+        const int t = max(t0 + (lane >> 1), 0);
         const uint32_t off = (uint32_t)((t * a.B + b0) * 4 + (lane & 1) * 16);
-        if constexpr (L::NW == 4) {
-            blds16_nt(w == 0 ? rs.act : w == 1 ? rs.rew : w == 2 ? rs.disc : rs.val, off, base + L::SCO + w * 1024);
-        } else {
-            const char* arr = s == 0 ? (const char*)a.act
-                              : s == 1 ? (const char*)a.rew
-                              : s == 2 ? (const char*)a.disc
-                                       : (const char*)a.val;
-            glds16(arr + ((size_t)t * a.B + b0) * 4 + (lane & 1) * 16, base + L::SCO + w * 1024);
-        }
+        blds16_nt(w == 0 ? rs.act : w == 1 ? rs.rew : w == 2 ? rs.disc : rs.val, off, base + L::SCO + w * 1024);
         ++n;
     }
     return n;
-}
-
-// v from lane ^ S, in VALU cross-lane ops (no LDS round trip): S = 8 by DPP row_ror:8 inside
-// each 16-lane row, S = 16 / 32 by gfx950's v_permlane16_swap / v_permlane32_swap
-template <int S>
-__device__ __forceinline__ float vt_xor(float v, int lane) {
-    const unsigned u = __float_as_uint(v);
-    if constexpr (S == 8) {
-        return __uint_as_float(__builtin_amdgcn_update_dpp(0u, u, 0x128, 0xf, 0xf, false));
-    } else if constexpr (S == 16) {
-        const auto q = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-        return __uint_as_float((lane & 16) ? q[0] : q[1]);
-    } else {
-        const auto q = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-        return __uint_as_float((lane & 32) ? q[0] : q[1]);
-    }
-}
-template <int S>
-__device__ __forceinline__ void vt_xscan_step(float& sd, float& sg, float& ed, float& eg, int lane) {
-    const float pd = vt_xor<S>(sd, lane), pg = vt_xor<S>(sg, lane);
-    const bool later = (lane & S) == 0;  // partner segment holds later rows
-    ed = later ? ed + eg * pd : ed;
-    eg = later ? eg * pg : eg;
-    sd = later ? sd + sg * pd : pd + pg * sd;
-    sg = sg * pg;
 }
 
 template <int A>
@@ -306,17 +444,14 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
     int mark = issued;  // VMEM ops issued once the chunk being waited for was queued
     const fi_vtrace_hparams hp = a.hp;
 
-    float pg = 0.f, base = 0.f, ent = 0.f;
-#define VT_STAMP()
+    VtLoss loss = {0.f, 0.f, 0.f};
     for (int k = 0; k < nchunks; ++k) {
         const int slot = k & 1;
         const int t0 = T - L::TC * (k + 1);
         wait_vmcnt(issued - mark);
         lds_barrier();  // B1: chunk k landed for every wave; slot (k+1)&1 fully consumed
-        VT_STAMP();
         const bool more = k + 1 < nchunks;
         if (more) issued += vt_issue_chunk<A, 0, G1>(a, rs, lds0, slot ^ 1, t0 - L::TC, b0, w, lane);
-        VT_STAMP();
         char* sl = smem + slot * L::SLOT;
         float* zpi = (float*)sl + tl * L::ROWF + c * A;
         float* zmu = (float*)(sl + L::LOGB) + tl * L::ROWF + c * A;
@@ -327,63 +462,23 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
         const int t = t0 + tl;
         const bool valid = t >= 0;
 
-        // packed-fp32 softmax statistics: e_i = 2^(z_i log2e - max log2e) (one v_pk_fma +
-        // one v_exp_f32 per logit), pi_i = e_i / sum e, H = sum pi log pi = (sum e z)/sum e - lse
-        f32x2 zp2[A / 2], zm2[A / 2];
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            zp2[i] = *(const f32x2*)(zpi + 2 * i);
-            zm2[i] = *(const f32x2*)(zmu + 2 * i);
-        }
-        int at = sact[tl * L::NB + c];
-        if (valid && (unsigned)at >= (unsigned)A) atomicAdd(a.bad, 1);
-        at = at < 0 ? 0 : (at >= A ? A - 1 : at);
-        const float zpa = zpi[at], zma = zmu[at];
+        VtRow<A, true> row;
+        vt_row_load(row, zpi, zmu, &sact[tl * L::NB + c], valid, a.bad);
         const float rw = srew[tl * L::NB + c];
         const float g = sdisc[tl * L::NB + c];
         const float v = sval[tl * L::NB + c];
         const float vn = (tl == L::TC - 1) ? vnext : sval[(tl + 1) * L::NB + c];
         const float vrow0 = sval[c];  // V at this chunk's first row: next chunk's vnext
-
-        float mx = vt_max3(zp2[0].x, zp2[0].y, zp2[0].y), mm = vt_max3(zm2[0].x, zm2[0].y, zm2[0].y);
-#pragma unroll
-        for (int i = 1; i < A / 2; ++i) {
-            mx = vt_max3(mx, zp2[i].x, zp2[i].y);
-            mm = vt_max3(mm, zm2[i].x, zm2[i].y);
-        }
-        const f32x2 nmx = {-mx * L2E, -mx * L2E}, nmm = {-mm * L2E, -mm * L2E};
-        f32x2 e2[A / 2];
-        f32x2 sp2 = {0.f, 0.f}, sm2 = {0.f, 0.f}, sz2 = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            const f32x2 ap = zp2[i] * L2E + nmx;
-            const f32x2 am = zm2[i] * L2E + nmm;
-            e2[i] = f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
-            sp2 += e2[i];
-            sz2 += e2[i] * zp2[i];
-            sm2 += f32x2{VT_EXP2(am.x), VT_EXP2(am.y)};
-        }
+        vt_row_exp(row);
         if (more) issued += vt_issue_chunk<A, G1, G2>(a, rs, lds0, slot ^ 1, t0 - L::TC, b0, w, lane);
-        const float sp = sp2.x + sp2.y, sm = sm2.x + sm2.y;
-        const float lse = mx + VT_LOG2(sp) * LN2, lsem = mm + VT_LOG2(sm) * LN2;
-        const float inv = __builtin_amdgcn_rcpf(sp);
-        const float plogp = (sz2.x + sz2.y) * inv - lse;
-        const float lpa = zpa - lse, lma = zma - lsem;
-        const float ratio = VT_EXP(lpa - lma);
-        const float rho = fminf(hp.rho_bar, ratio);
-        const float cc = hp.lambda_ * fminf(hp.c_bar, ratio);
-        const float pgr = fminf(hp.pg_rho_bar, ratio);
-        float d = valid ? rho * (rw + g * vn - v) : 0.f;
-        float gg = valid ? g * cc : 1.f;
+        vt_row_weights(row, hp);
+        const VtAffine own = vt_row_affine(valid, row.rho, row.cc, rw, g, v, vn);
 
-        // butterfly over the wave's 8 rows (lane ^ 8, ^ 16, ^ 32): (sd, sg) = the composition
-        // of the lane's current row segment, (ed, eg) = the composition of the rows after this
-        // one inside it; at the end (sd, sg) is the wave total in every row
-        const float d_own = d, g_own = gg;
-        float ed = 0.f, eg = 1.f;
-        vt_xscan_step<8>(d, gg, ed, eg, lane);
-        vt_xscan_step<16>(d, gg, ed, eg, lane);
-        vt_xscan_step<32>(d, gg, ed, eg, lane);
+        // butterfly over the wave's 8 rows (lane ^ 8, ^ 16, ^ 32)
+        float d = own.d, gg = own.g, ed = 0.f, eg = 1.f;
+        vt_scan_step<8, VtXorDpp>(d, gg, ed, eg, lane);
+        vt_scan_step<16, VtXorDpp>(d, gg, ed, eg, lane);
+        vt_scan_step<32, VtXorDpp>(d, gg, ed, eg, lane);
         if (more) issued += vt_issue_chunk<A, G2, NP>(a, rs, lds0, slot ^ 1, t0 - L::TC, b0, w, lane);
         mark = issued;  // the wait for chunk k+1 ignores the stores issued after this point
         // wave total -> this wave's own first mu row (no other wave reads it)
@@ -393,7 +488,6 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
             tot[8 + c] = gg;
         }
         lds_barrier();  // B2: wave totals visible
-        VT_STAMP();
 
         float acc_in = carry;  // acc at row 8(w+1): compose the later waves onto the carry
         float carry_new = carry;
@@ -404,39 +498,22 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
             if (w2 == w + 1) acc_in = carry_new;
         }
         if (w == L::NW - 1) acc_in = carry;
-        const float acc_nx = ed + eg * acc_in;
-        const float acc = d_own + g_own * acc_nx;
-        const float vs_t = v + acc;
-        const float vs_n = vn + acc_nx;
-        const float adv = pgr * (rw + g * vs_n - v);
-        const float dv = -hp.baseline_cost * acc;
+        const VtTargets o = vt_row_targets(own.d, own.g, ed + eg * acc_in, v, vn, rw, g, row.pgr, hp.baseline_cost);
         carry = carry_new;
         vnext = vrow0;
 
-        // dlogits over this wave's own pi rows:
-        //   dz_i = pi_i (adv + ec (log pi_i - H)) - adv [i = a_t] = e_i (alpha + beta z_i) - adv [i = a_t]
-        {
-            const float ec = hp.entropy_cost;
-            const float al = inv * (adv - ec * (plogp + lse)), be = inv * ec;
-            const f32x2 al2 = {al, al};
-#pragma unroll
-            for (int i = 0; i < A / 2; ++i) *(f32x2*)(zpi + 2 * i) = e2[i] * (zp2[i] * be + al2);
-            zpi[at] -= adv;
-        }
-        if (valid) {
-            pg += -adv * lpa;
-            base += 0.5f * acc * acc;
-            ent += plogp;
-        }
+        // dlogits over this wave's own pi rows (rows with t < 0 too: nothing reads or stores them)
+        vt_row_dlogits(row, zpi, o.adv, hp.entropy_cost);
+        if (valid) loss = vt_row_losses(loss, o.adv, row.lpa, o.acc, row.plogp);
         // Stores. Every chunk but the last (the only one holding t < 0) stores with the full
         // wave, so the per-wave VMEM count used by the next chunk's wait is exact; the last
         // chunk masks freely (nothing waits on its count). Rows: vs/pg_adv/dvalue 32 B per
         // t-row of the block, merged with the neighbouring blocks' segments in L2.
         if (valid) {
             const size_t e = (size_t)t * B + b;
-            VT_ST(vs_t, a.vs + e);
-            VT_ST(adv, a.adv + e);
-            VT_ST(dv, a.dval + e);
+            a.vs[e] = o.vs_t;
+            a.adv[e] = o.adv;
+            a.dval[e] = o.dv;
         }
         issued += 3;
         {  // this wave's 8 dlogits rows (8 * 2A float4 = 4 full-wave x4 stores + one x2)
@@ -447,8 +524,7 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
 #pragma unroll
             for (int i = 0; i < NF4; ++i) {
                 const int q = i * 64 + lane, rr = q / R4, c4 = q - rr * R4;
-                if (t0 + 8 * w + rr >= 0)
-                    VT_ST(((const f32x4*)srcf)[q], (f32x4*)(dst0 + (size_t)rr * B * A) + c4);
+                if (t0 + 8 * w + rr >= 0) ((f32x4*)(dst0 + (size_t)rr * B * A))[c4] = ((const f32x4*)srcf)[q];
             }
             issued += NF4;
             constexpr int REM2 = (N4 - NF4 * 64) * 2;  // remaining float2 (0..126)
@@ -458,21 +534,19 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
                     const int q2 = NF4 * 128 + i * 64 + lane;  // float2 index
                     const int rr = q2 / (2 * R4), c2 = q2 - rr * 2 * R4;
                     if (i * 64 + lane < REM2 && t0 + 8 * w + rr >= 0)
-                        VT_ST(((const f32x2*)srcf)[q2], (f32x2*)(dst0 + (size_t)rr * B * A) + c2);
+                        ((f32x2*)(dst0 + (size_t)rr * B * A))[c2] = ((const f32x2*)srcf)[q2];
                 }
                 issued += (REM2 + 63) / 64;
             }
         }
-        VT_STAMP();
     }
     // no vmcnt(0) here: the last chunk issues no LDS-DMA (only global stores are in flight),
     // so the loss-partial reduction below can overlap the store drain
-    VT_STAMP();
     __syncthreads();
     // per-workgroup loss partials; summed in a fixed order by vtrace_finalize_kernel or, in
     // the learner step, by the gradient-norm kernel that runs anyway (no extra launch, no
     // serial tail at the end of this kernel)
-    block_reduce3((double)pg, (double)base, (double)ent, (double*)smem, a.part + (size_t)blockIdx.x * 3);
+    block_reduce3((double)loss.pg, (double)loss.base, (double)loss.ent, (double*)smem, a.part + (size_t)blockIdx.x * 3);
 }
 
 // ------------------------------------------------------------------------------------
@@ -492,29 +566,34 @@ __global__ __launch_bounds__(64 * VtLayout<A>::NW, VtLayout<A>::WPS) void vtrace
 // same VMEM count per group and the wait for group g+1's DMA leaves group g's stores in flight.
 // Requires T <= 127 (thread row T writes the bootstrap dvalue), B % 4 == 0, even A <= 20.
 // ------------------------------------------------------------------------------------
-template <int A>
-struct VtStr {
-    static constexpr int NC = 4;                        // batch columns per group
-    static constexpr int NT = 512;                      // threads: (t, c) = (tid >> 2, tid & 3)
-    static constexpr int TMAX = NT / NC - 1;            // 127 (thread row T carries the bootstrap dvalue)
-    static constexpr int ROWB = NC * A * 4;             // bytes per t-row of a logits tile (288 at A=18)
-    static constexpr int PPR = ROWB / 16;               // 16-B pieces per t-row
-    static constexpr int NW = NT / 64;                  // 8 waves
-    static constexpr int NST = 4 + 3;                   // stores per wave per group (dlogits + vs/adv/dval)
-    static_assert(A % 2 == 0 && ROWB % 16 == 0, "pieces");
-    __host__ __device__ static constexpr int logp(int T) { return (T * ROWB + 1023) / 1024; }  // pieces per logits tile
-    __host__ __device__ static constexpr int scp(int T) { return (T * 16 + 1023) / 1024; }      // per scalar tile
+struct VtStrDim {  // what does not need A at compile time: the kernel and str_supported share it
+    static constexpr int NC = 4;              // batch columns per group
+    static constexpr int NT = 512;            // threads: (t, c) = (tid >> 2, tid & 3)
+    static constexpr int TMAX = NT / NC - 1;  // 127 (thread row T carries the bootstrap dvalue)
+    static constexpr int NW = NT / 64;        // 8 waves
+    static constexpr int NST = 4 + 3;         // stores per wave per group (dlogits + vs/adv/dval)
+    // a slot in 1-KiB DMA pieces: pi | mu (T rows x NC * A floats) | act | rew | disc (T rows x 16 B) | val (T + 1 rows)
+    __host__ __device__ static constexpr int rowb(int A) { return NC * A * 4; }
+    __host__ __device__ static constexpr int logp(int T, int A) { return (T * rowb(A) + 1023) / 1024; }
+    __host__ __device__ static constexpr int scp(int T) { return (T * 16 + 1023) / 1024; }
     __host__ __device__ static constexpr int valp(int T) { return ((T + 1) * 16 + 1023) / 1024; }
-    __host__ __device__ static constexpr int pieces(int T) { return 2 * logp(T) + 3 * scp(T) + valp(T); }
-    __host__ __device__ static constexpr int slot_bytes(int T) { return 1024 * pieces(T); }
-    __host__ __device__ static constexpr int lds_bytes(int T) { return 2 * slot_bytes(T) + NW * NC * 2 * 4; }
+    __host__ __device__ static constexpr int pieces(int T, int A) { return 2 * logp(T, A) + 3 * scp(T) + valp(T); }
+    __host__ __device__ static constexpr int slot_bytes(int T, int A) { return 1024 * pieces(T, A); }
+    // two slots | wave totals [NW][NC][2]
+    __host__ __device__ static constexpr int lds_bytes(int T, int A) { return 2 * slot_bytes(T, A) + NW * NC * 2 * 4; }
+};
+template <int A>
+struct VtStr : VtStrDim {
+    static constexpr int ROWB = rowb(A);   // bytes per t-row of a logits tile (288 at A=18)
+    static constexpr int PPR = ROWB / 16;  // 16-B pieces per t-row
+    static_assert(A % 2 == 0 && ROWB % 16 == 0, "pieces");
 };
 
 // piece j (< pieces(T)) of group b0's slot: the tensor it comes from and the byte offsets
 template <int A>
 __device__ __forceinline__ void vt_str_issue(const VtRsrc& rs, uint32_t slot_lds, int T, int B, int b0, int w, int lane) {
     using L = VtStr<A>;
-    const int LP = L::logp(T), SP = L::scp(T), NPc = L::pieces(T);
+    const int LP = L::logp(T, A), SP = L::scp(T), NPc = L::pieces(T, A);
     const int per_wave = (NPc + L::NW - 1) / L::NW;
     for (int i = 0; i < per_wave; ++i) {
         int j = w + L::NW * i;
@@ -522,7 +601,7 @@ __device__ __forceinline__ void vt_str_issue(const VtRsrc& rs, uint32_t slot_lds
         // own first one, or, where a short sequence has fewer pieces than waves, piece w - NPc --
         // never a piece past the slot, which would land in the other slot or in tot. pieces(T) >= 6
         // for every T >= 1 (2 logits + 3 scalar + 1 value piece), so 0 <= w - NPc < NW - 6 <= NPc
-        static_assert(L::pieces(1) == 6 && L::NW - 6 <= 6, "pad piece w - NPc must exist");
+        static_assert(L::pieces(1, A) == 6 && L::NW - 6 <= 6, "pad piece w - NPc must exist");
         if (j >= NPc) j = w < NPc ? w : w - NPc;
         const int q0 = 16 * lane;
         if (j < 2 * LP) {  // pi | mu
@@ -543,18 +622,6 @@ __device__ __forceinline__ void vt_str_issue(const VtRsrc& rs, uint32_t slot_lds
     }
 }
 
-template <int S>
-__device__ __forceinline__ float vt_shx(float v) { return __shfl_xor(v, S, 64); }
-template <int S>
-__device__ __forceinline__ void vt_str_scan_step(float& sd, float& sg, float& ed, float& eg, int lane) {
-    const float pd = vt_shx<S>(sd), pg = vt_shx<S>(sg);
-    const bool later = (lane & S) == 0;  // the partner segment holds later rows
-    ed = later ? ed + eg * pd : ed;
-    eg = later ? eg * pg : eg;
-    sd = later ? sd + sg * pd : pd + pg * sd;
-    sg = sg * pg;
-}
-
 template <int A>
 __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
     using L = VtStr<A>;
@@ -565,12 +632,12 @@ __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
     const bool valid = tt < T;
     const int G = gridDim.x, lg = xcd_remap(blockIdx.x, G);
     const int ngroups = B / L::NC;
-    const int SB = L::slot_bytes(T), LP = L::logp(T), SP = L::scp(T);
+    const int SB = L::slot_bytes(T, A), LP = L::logp(T, A), SP = L::scp(T);
     const uint32_t lds0 = lds_addr(vsm);
     float* tot = (float*)(vsm + 2 * SB);  // [NW][NC][2] wave totals
     const VtRsrc rs = vt_rsrc(a);
     const fi_vtrace_hparams hp = a.hp;
-    float pg = 0.f, base = 0.f, ent = 0.f;
+    VtLoss loss = {0.f, 0.f, 0.f};
     float* const sink = a.sink + tid;
     int k = 0;
     if (lg < ngroups) vt_str_issue<A>(rs, lds0, T, B, L::NC * lg, w, lane);
@@ -582,7 +649,7 @@ __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
         lds_barrier();  // B1: every wave's pieces landed; the other slot's last reads are done
         if (grp + G < ngroups) vt_str_issue<A>(rs, lds0 + ((k + 1) & 1) * SB, T, B, L::NC * (grp + G), w, lane);
 
-        // ---- A: carry-independent work of row (tt, b)
+        // ---- A: carry-independent work of row (tt, b); a thread row past T works on row 0
         const int tr = valid ? tt : 0;
         float* zpi = (float*)(sl + tr * L::ROWB + c * A * 4);
         const float* zmu = (const float*)(sl + 1024 * LP + tr * L::ROWB + c * A * 4);
@@ -590,52 +657,19 @@ __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
         const float* srew = (const float*)(sl + 2048 * LP + 1024 * SP);
         const float* sdisc = (const float*)(sl + 2048 * LP + 2048 * SP);
         const float* sval = (const float*)(sl + 2048 * LP + 3072 * SP);
-        f32x2 zp2[A / 2], zm2[A / 2];
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            zp2[i] = *(const f32x2*)(zpi + 2 * i);
-            zm2[i] = *(const f32x2*)(zmu + 2 * i);
-        }
-        int at = sact[4 * tr + c];
-        if (valid && (unsigned)at >= (unsigned)A) atomicAdd(a.bad, 1);
-        at = at < 0 ? 0 : (at >= A ? A - 1 : at);
-        const float zpa = zpi[at], zma = zmu[at];
+        VtRow<A, false> row;
+        vt_row_load(row, zpi, zmu, &sact[4 * tr + c], valid, a.bad);
         const float rw = srew[4 * tr + c], g = sdisc[4 * tr + c], v = sval[4 * tr + c], vn = sval[4 * tr + 4 + c];
-        float mx = vt_max3(zp2[0].x, zp2[0].y, zp2[0].y), mm = vt_max3(zm2[0].x, zm2[0].y, zm2[0].y);
-#pragma unroll
-        for (int i = 1; i < A / 2; ++i) {
-            mx = vt_max3(mx, zp2[i].x, zp2[i].y);
-            mm = vt_max3(mm, zm2[i].x, zm2[i].y);
-        }
-        const f32x2 nmx = {-mx * L2E, -mx * L2E}, nmm = {-mm * L2E, -mm * L2E};
-        f32x2 sp2 = {0.f, 0.f}, sm2 = {0.f, 0.f}, sz2 = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            const f32x2 ap = zp2[i] * L2E + nmx;
-            const f32x2 am = zm2[i] * L2E + nmm;
-            const f32x2 e = f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
-            sp2 += e;
-            sz2 += e * zp2[i];
-            sm2 += f32x2{VT_EXP2(am.x), VT_EXP2(am.y)};
-        }
-        const float sp = sp2.x + sp2.y, sm = sm2.x + sm2.y;
-        const float lse = mx + VT_LOG2(sp) * LN2, lsem = mm + VT_LOG2(sm) * LN2;
-        const float inv = __builtin_amdgcn_rcpf(sp);
-        const float plogp = (sz2.x + sz2.y) * inv - lse;
-        const float lpa = zpa - lse, lma = zma - lsem;
-        const float ratio = VT_EXP(lpa - lma);
-        const float rho = fminf(hp.rho_bar, ratio);
-        const float cc = hp.lambda_ * fminf(hp.c_bar, ratio);
-        const float pgr = fminf(hp.pg_rho_bar, ratio);
-        const float d_own = valid ? rho * (rw + g * vn - v) : 0.f;
-        const float g_own = valid ? g * cc : 1.f;
+        vt_row_exp(row);
+        vt_row_weights(row, hp);
+        const VtAffine own = vt_row_affine(valid, row.rho, row.cc, rw, g, v, vn);
 
         // ---- B: reverse affine scan over t (rows 16w .. 16w + 15 of this wave, 4 lanes apart)
-        float sd = d_own, sg = g_own, ed = 0.f, eg = 1.f;
-        vt_str_scan_step<4>(sd, sg, ed, eg, lane);
-        vt_str_scan_step<8>(sd, sg, ed, eg, lane);
-        vt_str_scan_step<16>(sd, sg, ed, eg, lane);
-        vt_str_scan_step<32>(sd, sg, ed, eg, lane);
+        float sd = own.d, sg = own.g, ed = 0.f, eg = 1.f;
+        vt_scan_step<4, VtXorShfl>(sd, sg, ed, eg, lane);
+        vt_scan_step<8, VtXorShfl>(sd, sg, ed, eg, lane);
+        vt_scan_step<16, VtXorShfl>(sd, sg, ed, eg, lane);
+        vt_scan_step<32, VtXorShfl>(sd, sg, ed, eg, lane);
         if (lane < L::NC) {
             tot[(w * L::NC + c) * 2] = sd;
             tot[(w * L::NC + c) * 2 + 1] = sg;
@@ -645,48 +679,28 @@ __global__ __launch_bounds__(512, 1) void vtrace_stream_kernel(VtArgs a) {
 #pragma unroll
         for (int w2 = L::NW - 1; w2 > 0; --w2)
             if (w2 > w) acc_in = tot[(w2 * L::NC + c) * 2] + tot[(w2 * L::NC + c) * 2 + 1] * acc_in;
-        const float acc_nx = ed + eg * acc_in;
-        const float acc = d_own + g_own * acc_nx;
 
         // ---- C: targets, gradients, stores
-        const float vs_t = v + acc;
-        const float vs_n = vn + acc_nx;
-        const float adv = pgr * (rw + g * vs_n - v);
-        const float dv = -hp.baseline_cost * acc;
-        {  // dlogits over this thread's own pi row
-            const float ec = hp.entropy_cost;
-            const float al = inv * (adv - ec * (plogp + lse)), be = inv * ec;
-            const f32x2 al2 = {al, al};
-#pragma unroll
-            for (int i = 0; i < A / 2; ++i) {
-                const f32x2 ap = zp2[i] * L2E + nmx;
-                const f32x2 e = f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
-                if (valid) *(f32x2*)(zpi + 2 * i) = e * (zp2[i] * be + al2);
-            }
-            if (valid) zpi[at] -= adv;
-        }
-        if (valid) {
-            pg += -adv * lpa;
-            base += 0.5f * acc * acc;
-            ent += plogp;
-        }
+        const VtTargets o = vt_row_targets(own.d, own.g, ed + eg * acc_in, v, vn, rw, g, row.pgr, hp.baseline_cost);
+        if (valid) vt_row_dlogits(row, zpi, o.adv, hp.entropy_cost);
+        if (valid) loss = vt_row_losses(loss, o.adv, row.lpa, o.acc, row.plogp);
         {  // vs / pg_adv / dvalue of the thread's row; thread row T writes the bootstrap dvalue 0
             const size_t e = (size_t)tt * B + b;
-            VT_ST(vs_t, valid ? a.vs + e : sink);
-            VT_ST(adv, valid ? a.adv + e : sink);
-            VT_ST(valid ? dv : 0.f, tt <= T ? a.dval + e : sink);
+            *(valid ? a.vs + e : sink) = o.vs_t;
+            *(valid ? a.adv + e : sink) = o.adv;
+            *(tt <= T ? a.dval + e : sink) = valid ? o.dv : 0.f;
         }
         lds_barrier();  // B3: the dlogits rows are complete
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // the tile's T * PPR pieces, 4 rounds of 512
             const int q = L::NT * i + tid;
-            const int row = q / L::PPR, pc = q - row * L::PPR;
+            const int row_q = q / L::PPR, pc = q - row_q * L::PPR;
             const f32x4 d4 = *(const f32x4*)(sl + 16 * (q < T * L::PPR ? q : 0));
-            VT_ST(d4, q < T * L::PPR ? (f32x4*)(a.dlog + (size_t)(row * B + b0) * A) + pc : (f32x4*)(a.sink + 4 * tid));
+            *(q < T * L::PPR ? (f32x4*)(a.dlog + (size_t)(row_q * B + b0) * A) + pc : (f32x4*)(a.sink + 4 * tid)) = d4;
         }
     }
     __syncthreads();
-    block_reduce3((double)pg, (double)base, (double)ent, (double*)vsm, a.part + (size_t)blockIdx.x * 3);
+    block_reduce3((double)loss.pg, (double)loss.base, (double)loss.ent, (double*)vsm, a.part + (size_t)blockIdx.x * 3);
 }
 
 // ------------------------------------------------------------------------------------
@@ -750,8 +764,7 @@ __device__ __forceinline__ void vt_affine_step(float& D, float& G) {
 // (FI_OOB) into the slot's padding, so every instruction issues with all lanes. Offsets need a
 // constant division (by 9) only; the stores' vmcnt bookkeeping does not depend on this count.
 template <int A>
-__device__ __forceinline__ void vt_seq_issue(const fi_i32x4 (&rs)[6], uint32_t slot_lds, int T, int B, int w,
-                                             int lane, int b0) {
+__device__ __forceinline__ void vt_seq_issue(const VtRsrc& rs, uint32_t slot_lds, int T, int B, int w, int lane, int b0) {
     using L = VtSeq<A>;
     const int np = T * L::PPR, nl = (np + 63) / 64;
     const uint32_t dl = (uint32_t)b0 * A * 4;
@@ -759,11 +772,11 @@ __device__ __forceinline__ void vt_seq_issue(const fi_i32x4 (&rs)[6], uint32_t s
         const int q = 64 * ii + lane;
         const int row = q / L::PPR, pc = q - row * L::PPR;
         const uint32_t voff = q < np ? (uint32_t)(row * B * A * 4 + pc * 16) + dl : FI_OOB;
-        blds16(rs[0], voff, __builtin_amdgcn_readfirstlane(slot_lds + 1024 * ii));
-        blds16(rs[1], voff, __builtin_amdgcn_readfirstlane(slot_lds + L::tile_bytes(T) + 1024 * ii));
+        blds16(rs.pi, voff, __builtin_amdgcn_readfirstlane(slot_lds + 1024 * ii));
+        blds16(rs.mu, voff, __builtin_amdgcn_readfirstlane(slot_lds + L::tile_bytes(T) + 1024 * ii));
     }
     const int lim = w < 3 ? 2 * T : 2 * (T + 1), ncl = (2 * (T + 1) + 63) / 64;
-    fi_i32x4 rc = w == 0 ? rs[2] : (w == 1 ? rs[3] : (w == 2 ? rs[4] : rs[5]));
+    fi_i32x4 rc = w == 0 ? rs.act : (w == 1 ? rs.rew : (w == 2 ? rs.disc : rs.val));
 #pragma unroll
     for (int e = 0; e < 4; ++e) rc[e] = __builtin_amdgcn_readfirstlane(rc[e]);
     const uint32_t cbase = slot_lds + 2 * L::tile_bytes(T) + w * L::col_bytes(T);
@@ -789,23 +802,14 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
     const int SB = L::slot_bytes(T);
     float* const tot = (float*)(vsm + 2 * SB);
     const uint32_t lds0 = lds_addr(vsm);
-    fi_i32x4 rs[6];
-    {
-        const uint32_t lbytes = (uint32_t)T * B * A * 4, sbytes = (uint32_t)T * B * 4;
-        rs[0] = make_rsrc(a.pi, lbytes);
-        rs[1] = make_rsrc(a.mu, lbytes);
-        rs[2] = make_rsrc(a.act, sbytes);
-        rs[3] = make_rsrc(a.rew, sbytes);
-        rs[4] = make_rsrc(a.disc, sbytes);
-        rs[5] = make_rsrc(a.val, sbytes + (uint32_t)B * 4);
-    }
+    const VtRsrc rs = vt_rsrc(a);
     const fi_vtrace_hparams hp = a.hp;
     // per-wave store instructions of one pair: vs, adv, dval + this wave's dlogits pieces
     const int np = T * L::PPR;
     int n_dl = 0;
     for (int i = w; 64 * i < np; i += 4) ++n_dl;
     const int n_st = 3 + n_dl;
-    float pg = 0.f, base = 0.f, ent = 0.f;
+    VtLoss loss = {0.f, 0.f, 0.f};
     float* const sink = a.sink + tid;  // stores of lanes with t >= T
 
     int k = 0;
@@ -820,58 +824,22 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
         if (p + G < npairs) vt_seq_issue<A>(rs, lds0 + ((k + 1) & 1) * SB, T, B, w, lane, L::NB * (p + G));
         if (tid < L::NB) a.dval[(size_t)T * B + b0 + tid] = 0.f;  // the bootstrap row (not counted: see below)
 
-        // scalars of the lane's (t, b)
+        // the lane's own row (tt, b): logits, scalars, softmax statistics
         const int* sact = (const int*)(sl + 2 * L::tile_bytes(T));
         const float* srew = (const float*)(sl + 2 * L::tile_bytes(T) + L::col_bytes(T));
         const float* sdisc = (const float*)(sl + 2 * L::tile_bytes(T) + 2 * L::col_bytes(T));
         const float* sval = (const float*)(sl + 2 * L::tile_bytes(T) + 3 * L::col_bytes(T));
-        int at = sact[2 * tt + c];
-        const float rw = srew[2 * tt + c], g = sdisc[2 * tt + c], v = sval[2 * tt + c], vn = sval[2 * tt + 2 + c];
-        if (valid && (unsigned)at >= (unsigned)A) atomicAdd(a.bad, 1);
-        at = at < 0 ? 0 : (at >= A ? A - 1 : at);
-
-        // softmax statistics of the lane's own row (as kernel 1)
         float* const zpi = (float*)(sl + (size_t)tt * L::ROWB) + c * A;
         const float* const zmu = (const float*)(sl + L::tile_bytes(T) + (size_t)tt * L::ROWB) + c * A;
-        f32x2 zp2[A / 2], zm2[A / 2];
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            zp2[i] = *(const f32x2*)(zpi + 2 * i);
-            zm2[i] = *(const f32x2*)(zmu + 2 * i);
-        }
-        const float zpa = zpi[at], zma = zmu[at];
-        float mx = vt_max3(zp2[0].x, zp2[0].y, zp2[0].y), mm = vt_max3(zm2[0].x, zm2[0].y, zm2[0].y);
-#pragma unroll
-        for (int i = 1; i < A / 2; ++i) {
-            mx = vt_max3(mx, zp2[i].x, zp2[i].y);
-            mm = vt_max3(mm, zm2[i].x, zm2[i].y);
-        }
-        const f32x2 nmx = {-mx * L2E, -mx * L2E}, nmm = {-mm * L2E, -mm * L2E};
-        f32x2 e2[A / 2];
-        f32x2 sp2 = {0.f, 0.f}, sm2 = {0.f, 0.f}, sz2 = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < A / 2; ++i) {
-            const f32x2 ap = zp2[i] * L2E + nmx;
-            const f32x2 am = zm2[i] * L2E + nmm;
-            e2[i] = f32x2{VT_EXP2(ap.x), VT_EXP2(ap.y)};
-            sp2 += e2[i];
-            sz2 += e2[i] * zp2[i];
-            sm2 += f32x2{VT_EXP2(am.x), VT_EXP2(am.y)};
-        }
-        const float sp = sp2.x + sp2.y, sm = sm2.x + sm2.y;
-        const float lse = mx + VT_LOG2(sp) * LN2, lsem = mm + VT_LOG2(sm) * LN2;
-        const float inv = __builtin_amdgcn_rcpf(sp);
-        const float plogp = (sz2.x + sz2.y) * inv - lse;
-        const float lpa = zpa - lse, lma = zma - lsem;
-        const float ratio = VT_EXP(lpa - lma);
-        const float rho = fminf(hp.rho_bar, ratio);
-        const float cc = hp.lambda_ * fminf(hp.c_bar, ratio);
-        const float pgr = fminf(hp.pg_rho_bar, ratio);
-        const float d_own = valid ? rho * (rw + g * vn - v) : 0.f;
-        const float g_own = valid ? g * cc : 1.f;
+        VtRow<A, true> row;
+        vt_row_load(row, zpi, zmu, &sact[2 * tt + c], valid, a.bad);
+        const float rw = srew[2 * tt + c], g = sdisc[2 * tt + c], v = sval[2 * tt + c], vn = sval[2 * tt + 2 + c];
+        vt_row_exp(row);
+        vt_row_weights(row, hp);
+        const VtAffine own = vt_row_affine(valid, row.rho, row.cc, rw, g, v, vn);
 
         // prefix composition in lane order (= reverse time) inside each 32-lane column half
-        float D = d_own, Gm = g_own;
+        float D = own.d, Gm = own.g;
         vt_affine_step<0x111>(D, Gm);       // row_shr:1
         vt_affine_step<0x112>(D, Gm);       // row_shr:2
         vt_affine_step<0x114>(D, Gm);       // row_shr:4
@@ -892,33 +860,15 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
 #pragma unroll
         for (int w2 = 3; w2 >= 0; --w2)
             if (w2 > w) x = tot[(w2 * 2 + 0) * L::NB + c] + tot[(w2 * 2 + 1) * L::NB + c] * x;
-        const float acc_nx = Dx + Gx * x;  // acc_{t+1}
-        const float acc = d_own + g_own * acc_nx;
-        const float vs_t = v + acc;
-        const float adv = pgr * (rw + g * (vn + acc_nx) - v);
-        const float dv = -hp.baseline_cost * acc;
+        const VtTargets o = vt_row_targets(own.d, own.g, Dx + Gx * x, v, vn, rw, g, row.pgr, hp.baseline_cost);
 
-        // dlogits over the lane's own pi row: dz_i = e_i (alpha + beta z_i) - adv [i = a_t]
-        {
-            const float ec = hp.entropy_cost;
-            const float al = inv * (adv - ec * (plogp + lse)), be = inv * ec;
-            const f32x2 al2 = {al, al};
-            if (valid) {
-#pragma unroll
-                for (int i = 0; i < A / 2; ++i) *(f32x2*)(zpi + 2 * i) = e2[i] * (zp2[i] * be + al2);
-                zpi[at] -= adv;
-            }
-        }
-        if (valid) {
-            pg += -adv * lpa;
-            base += 0.5f * acc * acc;
-            ent += plogp;
-        }
+        if (valid) vt_row_dlogits(row, zpi, o.adv, hp.entropy_cost);
+        if (valid) loss = vt_row_losses(loss, o.adv, row.lpa, o.acc, row.plogp);
         {  // every lane stores (the sink takes rows t >= T), so each wave issues exactly 3 here
             const size_t e = (size_t)tt * B + b;
-            VT_ST(vs_t, valid ? a.vs + e : sink);
-            VT_ST(adv, valid ? a.adv + e : sink);
-            VT_ST(dv, valid ? a.dval + e : sink);
+            *(valid ? a.vs + e : sink) = o.vs_t;
+            *(valid ? a.adv + e : sink) = o.adv;
+            *(valid ? a.dval + e : sink) = o.dv;
         }
         lds_barrier();  // B3: the slot's dlogits rows complete
 
@@ -926,9 +876,8 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
         for (int i = w; 64 * i < np; i += 4) {
             const int q = 64 * i + lane;
             if (q < np) {
-                const int row = q / L::PPR, pc = q - row * L::PPR;
-                const f32x4 d4 = *(const f32x4*)(sl + 16 * q);
-                VT_ST(d4, (f32x4*)(a.dlog + (size_t)(row * B + b0) * A) + pc);
+                const int row_q = q / L::PPR, pc = q - row_q * L::PPR;
+                ((f32x4*)(a.dlog + (size_t)(row_q * B + b0) * A))[pc] = *(const f32x4*)(sl + 16 * q);
             }
         }
         // the bootstrap-row store above is the one VMEM op not in n_st: it was issued BEFORE
@@ -936,7 +885,7 @@ __global__ __launch_bounds__(256, 2) void vtrace_seq_kernel(VtArgs a) {
     }
     __syncthreads();
     // per-workgroup loss partials (summed in a fixed order later, as kernel 1)
-    block_reduce3((double)pg, (double)base, (double)ent, (double*)(tot + 4 * 2 * L::NB),
+    block_reduce3((double)loss.pg, (double)loss.base, (double)loss.ent, (double*)(tot + 4 * 2 * L::NB),
                   a.part + (size_t)blockIdx.x * 3);
 }
 
@@ -972,22 +921,25 @@ static int* vt_bad_counter(void* ws, int B) {
     return (int*)((char*)ws + kSinkFloats * sizeof(float) + vt_part_bytes(B));
 }
 
-template <int A>
-static void launch_lds(const VtArgs& a, int nblk, hipStream_t s) {
-    hipLaunchKernelGGL(vtrace_lds_kernel<A>, dim3(nblk), dim3(64 * VtLayout<A>::NW), 0, s, a);
+// f(std::integral_constant<int, A>) for the run-time A, one of the even 2 .. 20 the LDS kernels
+// are compiled for
+template <int A0 = 2, class F>
+static int vt_dispatch_a(int A, F&& f) {
+    if constexpr (A0 > 20) {
+        return fail(FI_ERR_UNSUPPORTED, "vtrace: A not instantiated");
+    } else {
+        return A == A0 ? f(std::integral_constant<int, A0>{}) : vt_dispatch_a<A0 + 2>(A, f);
+    }
 }
-template <int A>
-static void launch_seq(const VtArgs& a, int nblk, hipStream_t s) {
-    hipLaunchKernelGGL(vtrace_seq_kernel<A>, dim3(nblk), dim3(VtSeq<A>::NT), VtSeq<A>::lds_bytes(a.T), s, a);
-}
-// persistent grid of the sequence kernel: two workgroups per CU (LDS: two pair slots each)
+
+// grid of a persistent kernel: a workgroup per group of `cols` columns, at most `per_cu` a CU
 // (the CU count is read from the calling thread's current device each time: handles on
 // different devices launch from their own threads, so no cached process-wide value)
-static int seq_grid(int B) {
+static int vt_persistent_grid(int B, int cols, int per_cu) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, std::min(B / 2, 2 * cus));
+    return std::max(1, std::min(B / cols, per_cu * cus));
 }
 
 static bool lds_supported(int A, int B) { return B % 8 == 0 && A % 2 == 0 && A >= 2 && A <= 20; }
@@ -1009,26 +961,15 @@ static int launch_str(const VtArgs& a, int nblk, hipStream_t s) {
                                         hipGetErrorString(e) + ")");
         raised.fetch_or(bit, std::memory_order_acq_rel);
     }
-    hipLaunchKernelGGL(vtrace_stream_kernel<A>, dim3(nblk), dim3(VtStr<A>::NT), VtStr<A>::lds_bytes(a.T), s, a);
+    hipLaunchKernelGGL(vtrace_stream_kernel<A>, dim3(nblk), dim3(VtStr<A>::NT), VtStrDim::lds_bytes(a.T, A), s, a);
     return FI_OK;
 }
-// persistent grid of the streaming kernel: one workgroup per CU (132 KB of LDS at T = 100)
-static int str_grid(int B) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, std::min(B / 4, cus));
-}
-// (the two slots hold the whole sequence of a group: T <= 124 at A = 18 within 160 KB of LDS)
-static int str_lds_bytes(int T, int A) {
-    const int logp = (T * 4 * A * 4 + 1023) / 1024, scp = (T * 16 + 1023) / 1024, valp = ((T + 1) * 16 + 1023) / 1024;
-    return 2 * 1024 * (2 * logp + 3 * scp + valp) + 8 * 4 * 2 * 4;
-}
-// the dlogits tile leaves in 4 rounds of NT = 512 pieces of 16 B (VtStr::NST counts them), so
-// T * PPR = T * A pieces must fit 2,048 (T <= 113 at A = 18, T <= 102 at A = 20)
+// The streaming kernel's two slots hold the whole sequence of a group (T <= 124 at A = 18 within
+// 160 KB of LDS), and the dlogits tile leaves in 4 rounds of NT = 512 pieces of 16 B (NST counts
+// them), so T * PPR = T * A pieces must fit 2,048 (T <= 113 at A = 18, T <= 102 at A = 20)
 static bool str_supported(int T, int A, int B) {
-    return B % 4 == 0 && A % 2 == 0 && A >= 2 && A <= 20 && T <= VtStr<2>::TMAX && T * A <= 4 * VtStr<2>::NT &&
-           str_lds_bytes(T, A) <= 160 * 1024;
+    return B % 4 == 0 && A % 2 == 0 && A >= 2 && A <= 20 && T <= VtStrDim::TMAX && T * A <= 4 * VtStrDim::NT &&
+           VtStrDim::lds_bytes(T, A) <= 160 * 1024;
 }
 
 int vtrace_launch(int variant, int T, int B, int A, const float* pi, const float* mu,
@@ -1059,80 +1000,44 @@ int vtrace_launch(int variant, int T, int B, int A, const float* pi, const float
     // kernel 1 ("V-trace: the whole-sequence kernel")
     const bool seq_ok = lds_supported(A, B) && fits32 && T <= 128 && B % 2 == 0;
     FI_REQUIRE(!(variant == 3 && !seq_ok), "vtrace: sequence kernel needs T<=128, B%8==0, even A<=20");
+    int nblk;
     if (variant == 3) {
         FI_REQUIRE(vs && adv, "vtrace: sequence kernel writes vs and pg_adv (non-null)");
         FI_REQUIRE(((uintptr_t)pi | (uintptr_t)mu | (uintptr_t)dlog) % 16 == 0, "vtrace: needs 16-byte aligned logits");
-        const int nblk = seq_grid(B);
-        switch (A) {
-            case 2: launch_seq<2>(a, nblk, stream); break;
-            case 4: launch_seq<4>(a, nblk, stream); break;
-            case 6: launch_seq<6>(a, nblk, stream); break;
-            case 8: launch_seq<8>(a, nblk, stream); break;
-            case 10: launch_seq<10>(a, nblk, stream); break;
-            case 12: launch_seq<12>(a, nblk, stream); break;
-            case 14: launch_seq<14>(a, nblk, stream); break;
-            case 16: launch_seq<16>(a, nblk, stream); break;
-            case 18: launch_seq<18>(a, nblk, stream); break;
-            case 20: launch_seq<20>(a, nblk, stream); break;
-            default: return fail(FI_ERR_UNSUPPORTED, "vtrace: A not instantiated");
-        }
-        FI_HIP_CHECK(hipGetLastError());
-        if (nblk_out) *nblk_out = nblk;
-        if (finalize) return vtrace_finalize_launch(ws, nblk, losses, stream, a.bad);
-        return FI_OK;
-    }
-    if (variant == 4) {
+        nblk = vt_persistent_grid(B, 2, 2);  // two workgroups per CU (LDS: two pair slots each)
+        FI_TRY(vt_dispatch_a(A, [&](auto ca) {
+            using L = VtSeq<decltype(ca)::value>;
+            hipLaunchKernelGGL(vtrace_seq_kernel<decltype(ca)::value>, dim3(nblk), dim3(L::NT), L::lds_bytes(T), stream, a);
+            return FI_OK;
+        }));
+    } else if (variant == 4) {
         FI_REQUIRE(str_supported(T, A, B) && fits32,
                    "vtrace: streaming kernel needs B%4==0, even A<=20, T*A<=2048 and the whole sequence of 4 columns in 160 KB of LDS");
         FI_REQUIRE(vs && adv, "vtrace: streaming kernel writes vs and pg_adv (non-null)");
         FI_REQUIRE(((uintptr_t)pi | (uintptr_t)mu | (uintptr_t)dlog) % 16 == 0 &&
                    ((uintptr_t)act | (uintptr_t)rew | (uintptr_t)disc | (uintptr_t)val) % 16 == 0,
                    "vtrace: streaming kernel needs 16-byte aligned tensors");
-        const int nblk = str_grid(B);
-        switch (A) {
-            case 2: FI_TRY(launch_str<2>(a, nblk, stream)); break;
-            case 4: FI_TRY(launch_str<4>(a, nblk, stream)); break;
-            case 6: FI_TRY(launch_str<6>(a, nblk, stream)); break;
-            case 8: FI_TRY(launch_str<8>(a, nblk, stream)); break;
-            case 10: FI_TRY(launch_str<10>(a, nblk, stream)); break;
-            case 12: FI_TRY(launch_str<12>(a, nblk, stream)); break;
-            case 14: FI_TRY(launch_str<14>(a, nblk, stream)); break;
-            case 16: FI_TRY(launch_str<16>(a, nblk, stream)); break;
-            case 18: FI_TRY(launch_str<18>(a, nblk, stream)); break;
-            case 20: FI_TRY(launch_str<20>(a, nblk, stream)); break;
-            default: return fail(FI_ERR_UNSUPPORTED, "vtrace: A not instantiated");
-        }
-        FI_HIP_CHECK(hipGetLastError());
-        if (nblk_out) *nblk_out = nblk;
-        if (finalize) return vtrace_finalize_launch(ws, nblk, losses, stream, a.bad);
-        return FI_OK;
-    }
-    bool use_lds = variant == 1 || (variant == 0 && lds_supported(A, B) && fits32);
-    FI_REQUIRE(!(variant == 1 && !lds_supported(A, B)), "vtrace: LDS kernel needs B%8==0, even A<=20");
-    FI_REQUIRE(!(variant == 1 && !fits32), "vtrace: LDS kernel needs T*B*A*4 < 2^31 bytes");
-    int nblk;
-    if (use_lds) {
-        FI_REQUIRE(vs && adv, "vtrace: LDS kernel writes vs and pg_adv (non-null)");
-        FI_REQUIRE(((uintptr_t)pi | (uintptr_t)mu | (uintptr_t)dlog) % 16 == 0 &&
-                   ((uintptr_t)act | (uintptr_t)rew | (uintptr_t)disc | (uintptr_t)val) % 16 == 0,
-                   "vtrace: LDS kernel needs 16-byte aligned tensors");
-        nblk = B / 8;
-        switch (A) {
-            case 2: launch_lds<2>(a, nblk, stream); break;
-            case 4: launch_lds<4>(a, nblk, stream); break;
-            case 6: launch_lds<6>(a, nblk, stream); break;
-            case 8: launch_lds<8>(a, nblk, stream); break;
-            case 10: launch_lds<10>(a, nblk, stream); break;
-            case 12: launch_lds<12>(a, nblk, stream); break;
-            case 14: launch_lds<14>(a, nblk, stream); break;
-            case 16: launch_lds<16>(a, nblk, stream); break;
-            case 18: launch_lds<18>(a, nblk, stream); break;
-            case 20: launch_lds<20>(a, nblk, stream); break;
-            default: return fail(FI_ERR_UNSUPPORTED, "vtrace: A not instantiated");
-        }
+        nblk = vt_persistent_grid(B, 4, 1);  // one workgroup per CU (132 KB of LDS at T = 100)
+        FI_TRY(vt_dispatch_a(A, [&](auto ca) { return launch_str<decltype(ca)::value>(a, nblk, stream); }));
     } else {
-        nblk = (B + 255) / 256;
-        hipLaunchKernelGGL(vtrace_column_kernel, dim3(nblk), dim3(256), 0, stream, a);
+        bool use_lds = variant == 1 || (variant == 0 && lds_supported(A, B) && fits32);
+        FI_REQUIRE(!(variant == 1 && !lds_supported(A, B)), "vtrace: LDS kernel needs B%8==0, even A<=20");
+        FI_REQUIRE(!(variant == 1 && !fits32), "vtrace: LDS kernel needs T*B*A*4 < 2^31 bytes");
+        if (use_lds) {
+            FI_REQUIRE(vs && adv, "vtrace: LDS kernel writes vs and pg_adv (non-null)");
+            FI_REQUIRE(((uintptr_t)pi | (uintptr_t)mu | (uintptr_t)dlog) % 16 == 0 &&
+                       ((uintptr_t)act | (uintptr_t)rew | (uintptr_t)disc | (uintptr_t)val) % 16 == 0,
+                       "vtrace: LDS kernel needs 16-byte aligned tensors");
+            nblk = B / 8;
+            FI_TRY(vt_dispatch_a(A, [&](auto ca) {
+                using L = VtLayout<decltype(ca)::value>;
+                hipLaunchKernelGGL(vtrace_lds_kernel<decltype(ca)::value>, dim3(nblk), dim3(64 * L::NW), 0, stream, a);
+                return FI_OK;
+            }));
+        } else {
+            nblk = (B + 255) / 256;
+            hipLaunchKernelGGL(vtrace_column_kernel, dim3(nblk), dim3(256), 0, stream, a);
+        }
     }
     FI_HIP_CHECK(hipGetLastError());
     if (nblk_out) *nblk_out = nblk;

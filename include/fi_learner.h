@@ -217,7 +217,11 @@ int fi_vtrace_loss_fp32(int T, int B, int A, const float* pi_logits, const float
                         const float* values, const fi_vtrace_hparams* hp, float* vs,
                         float* pg_adv, float* dlogits, float* dvalue, double* losses_dev,
                         void* workspace, size_t workspace_bytes, void* stream);
-/* variant: 0 = auto, 1 = LDS-staged scan kernel, 2 = one-column-per-lane kernel        */
+/* variant: 0 = auto (1 where the shape allows it, else 2), 1 = LDS-staged chunked scan kernel
+ * (B % 8 == 0, even A <= 20), 2 = one-column-per-lane kernel (any shape), 3 = whole-sequence
+ * kernel (as 1, T <= 128), 4 = streaming kernel (B % 4 == 0, even A <= 20, T <= 127,
+ * T * A <= 2048, the sequence of 4 columns in 160 KB of LDS). A variant asked for at a shape
+ * it does not take is refused with FI_ERR_INVALID.                                            */
 int fi_vtrace_loss_fp32_variant(int variant, int T, int B, int A, const float* pi_logits,
                                 const float* mu_logits, const int32_t* actions,
                                 const float* rewards, const float* discounts,

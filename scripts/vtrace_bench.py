@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--A", type=int, default=18)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--variant", type=int, action="append", default=[],
-                    help="kernel variant(s) to time (0 auto, 1 chunked LDS, 2 column, 3 whole-sequence)")
+                    help="kernel variant(s) to time (0 auto, 1 chunked LDS, 2 column, 3 whole-sequence, 4 streaming)")
     ap.add_argument("--sets", type=int, default=1, help="rotate over this many disjoint input/output sets (6: cold)")
     ap.add_argument("--stamps", action="store_true",
                     help="libs built with -DFI_VT_STAMPS: print per-phase timing of wave 0")
