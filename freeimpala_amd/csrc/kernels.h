@@ -285,11 +285,27 @@ void learner_set_popart_block(fi_learner* l, PopartBlock* block, void (*free_fn)
 struct KernelTagger;  // atari.h
 size_t surrogate_workspace_bytes(int T, int B, int A);  // 0 for a refused shape
 int surrogate_loss_blocks(int T, int B, int A);
+int surrogate_check_params(const std::string& who, const fi_surrogate_params* p);  // FI_ERR_INVALID, `who` opens the message
 int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
                      const float* disc, const float* val, const fi_vtrace_hparams& hp, const fi_surrogate_params& prm,
                      float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
                      int* bad, hipStream_t stream, KernelTagger* tg = nullptr, const double** partials = nullptr,
                      int* nblk_out = nullptr);
+
+// the rows and scan kernels alone, on (some logits, mu): vs and adv are written, and *out names what they
+// left in ws (a surrogate workspace) for a loss kernel of another file (target.hip): log rho per row, the
+// advantage moments' partials and pivot, the word the bad actions were counted into (bad, or one inside
+// ws, zeroed here) and the grid of the rows kernel, which a loss kernel over the same rows takes
+struct SurrogateFront {
+    const float* lr;      // [T * B]
+    const double* mom;    // [nscan][2]
+    const double* pivot;  // 1
+    int* bad;
+    int nscan, ct, slices, slice_len;
+};
+int surrogate_front_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                           const float* disc, const float* val, const fi_vtrace_hparams& hp, float* vs, float* adv, void* ws,
+                           size_t ws_bytes, int* bad, hipStream_t stream, KernelTagger* tg, SurrogateFront* out);
 
 // learner.cpp: a learner's surrogate block, made and freed by surrogate.hip, which hands its launcher
 // in with it (as popart.hip does): learner.cpp names nothing of surrogate.hip, so a library of the
@@ -314,6 +330,37 @@ struct SurrogateView {
 };
 int learner_surrogate_view(fi_learner* l, SurrogateView* out);
 void learner_set_surrogate_block(fi_learner* l, SurrogateBlock* block, void (*free_fn)(void*));
+
+// learner.cpp: a learner's target-network block (include/fi_target.h, where the rule stands), made and freed
+// by target.hip, which hands its launchers in with it: learner.cpp names nothing of target.hip, so a
+// library of the learner alone links. While the block is `on`: a step with the surrogate objective on runs
+// the target forward into tlogits / tvalues first and calls `launch` where it would call the surrogate's
+// launcher; every step whose update number is a multiple of `period` calls `update` behind the optimiser
+struct TargetBlock {
+    float* theta = nullptr;    // the target parameters, nparams floats
+    float* tlogits = nullptr;  // (T + 1, B, A)
+    float* tvalues = nullptr;  // (T + 1, B): scratch, not used
+    void* stats = nullptr;     // device, 32 bytes: uint64 updates, rows; double mean_log_r, mean_sq_log_r
+    void* ws = nullptr;
+    size_t ws_bytes = 0, nparams = 0;
+    bool on = false;
+    uint32_t period = 0;
+    float tau = 0.f;
+    int (*launch)(const TargetBlock*, const SurrogateBlock*, int T, int B, int A, const float* pi, const float* mu,
+                  const int32_t* act, const float* rew, const float* disc, const float* val, const fi_vtrace_hparams& hp,
+                  float* vs, float* adv, float* dlog, float* dval, int* bad, hipStream_t stream, KernelTagger* tg,
+                  const double** partials, int* nblk) = nullptr;
+    int (*update)(const TargetBlock*, const float* params, const int* skip, hipStream_t stream) = nullptr;
+};
+struct TargetView {
+    int dev, T, B, A, nranks;
+    size_t nparams;
+    const float* params;
+    hipStream_t stream;
+    TargetBlock* block;
+};
+int learner_target_view(fi_learner* l, TargetView* out);
+void learner_set_target_block(fi_learner* l, TargetBlock* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

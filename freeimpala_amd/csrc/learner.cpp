@@ -133,6 +133,9 @@ struct fi_learner {
     // the clipped surrogate objective (fi_surrogate.h): the block is surrogate.hip's, with its launcher
     SurrogateBlock* surrogate = nullptr;
     void (*surrogate_free)(void*) = nullptr;
+    // the target network (fi_target.h): the block is target.hip's, with its launchers
+    TargetBlock* target = nullptr;
+    void (*target_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -235,6 +238,7 @@ static void destroy(fi_learner* l) {
     if (l->diag) l->diag_free(l->diag);
     if (l->popart) l->popart_free(l->popart);
     if (l->surrogate) l->surrogate_free(l->surrogate);
+    if (l->target) l->target_free(l->target);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -417,8 +421,8 @@ static void mark(fi_learner* l, int phase) {
 struct Tag {
     fi_learner* l;
     int idx = -1;
-    Tag(fi_learner* l_, const char* name) : l(l_) {
-        if (!l->profiling) return;
+    Tag(fi_learner* l_, const char* name) : l(l_) {  // name == nullptr: no tag
+        if (!l->profiling || !name) return;
         if ((size_t)(2 * l->tag_used + 2) > l->tag_ev.size()) {
             hipEvent_t a = nullptr, b = nullptr;
             if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
@@ -514,17 +518,20 @@ struct BucketAllReduce : GradReadyHook {
     }
 };
 
-static int mlp_forward(fi_learner* l) {
+// params: the learner's slab, or another of its layout (the target network's, fi_target.h: its launches
+// carry no tags of their own, one tag stands around the call)
+static int mlp_forward(fi_learner* l, const float* params, float* logits, float* values) {
     const int D = l->D, H = l->H, A = l->A;
-    const float* W1 = l->params;
+    const bool own = params == l->params;
+    const float* W1 = params;
     const float* b1 = W1 + (size_t)D * H;
     const float* W2 = b1 + H;
     const float* b2 = W2 + (size_t)H * H;
     const float* Wh = b2 + H;
     const float* bh = Wh + (size_t)H * (A + 1);
-    { Tag t(l, "mlp_fwd_l1"); FI_TRY(f32_linear_fwd(l->obs, l->rows, D, W1, b1, H, true, l->h1, l->stream)); }
-    { Tag t(l, "mlp_fwd_l2"); FI_TRY(f32_linear_fwd(l->h1, l->rows, H, W2, b2, H, true, l->h2, l->stream)); }
-    { Tag t(l, "mlp_fwd_heads"); FI_TRY(f32_heads_fwd(l->h2, l->rows, H, Wh, bh, A, l->logits, l->values, l->stream)); }
+    { Tag t(l, own ? "mlp_fwd_l1" : nullptr); FI_TRY(f32_linear_fwd(l->obs, l->rows, D, W1, b1, H, true, l->h1, l->stream)); }
+    { Tag t(l, own ? "mlp_fwd_l2" : nullptr); FI_TRY(f32_linear_fwd(l->h1, l->rows, H, W2, b2, H, true, l->h2, l->stream)); }
+    { Tag t(l, own ? "mlp_fwd_heads" : nullptr); FI_TRY(f32_heads_fwd(l->h2, l->rows, H, Wh, bh, A, logits, values, l->stream)); }
     return FI_OK;
 }
 
@@ -651,6 +658,26 @@ static BatchTensors batch_tensors(const fi_learner* l) {
                         l->act,      l->rew, l->disc, l->bad, l->cols, l->versions, l->stream};
 }
 
+// The target network's logits of this batch (fi_target.h, 1.): the learner's own net and activations on
+// the target parameters, in front of the learner's forward, which overwrites the activations again
+static int target_forward(fi_learner* l) {
+    const TargetBlock* tb = l->target;
+    if (l->cfg.arch == FI_ARCH_MLP) {
+        Tag t(l, "target_forward");
+        return mlp_forward(l, tb->theta, tb->tlogits, tb->tvalues);
+    }
+    // the net points at theta- between the two syncs only: the way back is taken whatever the forward returned
+    int rc;
+    { Tag t(l, "target_weights_bf16"); rc = atari_sync_weights(l->atari, tb->theta, l->stream); }
+    if (rc == FI_OK) {
+        Tag t(l, "target_forward");
+        rc = atari_forward(l->atari, l->frames, tb->tlogits, tb->tvalues, l->stream, nullptr);
+    }
+    int back;
+    { Tag t(l, "target_weights_back"); back = atari_sync_weights(l->atari, l->params, l->stream); }
+    return rc != FI_OK ? rc : back;
+}
+
 static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
@@ -672,7 +699,9 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         FI_TRY(clip_rewards_launch(l->rew, (size_t)l->TB, l->reward_clip, l->stream));
     }
     mark(l, FI_PHASE_FORWARD);
-    if (l->cfg.arch == FI_ARCH_MLP) FI_TRY(mlp_forward(l));
+    const bool sur_on = l->surrogate && l->surrogate->on, tgt_on = l->target && l->target->on;
+    if (sur_on && tgt_on) FI_TRY(target_forward(l));
+    if (l->cfg.arch == FI_ARCH_MLP) FI_TRY(mlp_forward(l, l->params, l->logits, l->values));
     else {
         LearnerTagger tg(l);
         FI_TRY(atari_forward(l->atari, l->frames, l->logits, l->values, l->stream, l->profiling ? &tg : nullptr));
@@ -684,7 +713,13 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     mark(l, FI_PHASE_VTRACE);
     int vt_nblk = 0;
     const double* loss_part = nullptr;  // [vt_nblk][3], summed by the gradient-norm kernel
-    if (l->surrogate && l->surrogate->on) {
+    if (sur_on && tgt_on) {
+        // the surrogate around the target network (fi_target.h): the same outputs again
+        LearnerTagger tg(l);
+        FI_TRY(l->target->launch(l->target, l->surrogate, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc,
+                                 l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue, l->bad, l->stream,
+                                 l->profiling ? &tg : nullptr, &loss_part, &vt_nblk));
+    } else if (sur_on) {
         // the second objective (fi_surrogate.h) in V-trace's place: the same outputs, its own tags
         LearnerTagger tg(l);
         FI_TRY(l->surrogate->launch(l->surrogate, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc, l->values,
@@ -751,6 +786,11 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         float* w = l->params + l->nparams - O - (size_t)Hh * O + l->A;  // column A of the Hh x O weights
         FI_TRY(pa->update(l->vs, (size_t)l->TB, pa->state, w, (size_t)O, Hh, b, pa->beta, pa->sigma_min, pa->sigma_max,
                           l->bad, pa->ws, pa->ws_bytes, l->stream));
+    }
+    if (tgt_on && (uint64_t)step % l->target->period == 0) {
+        // the target moves towards the parameters this update left; skipped with the update
+        Tag t(l, "target_update");
+        FI_TRY(l->target->update(l->target, l->params, l->bad, l->stream));
     }
     if (l->atari) {
         Tag t(l, "weights_bf16");
@@ -1328,6 +1368,18 @@ int fi::learner_surrogate_view(fi_learner* l, SurrogateView* out) {
 void fi::learner_set_surrogate_block(fi_learner* l, SurrogateBlock* block, void (*free_fn)(void*)) {
     l->surrogate_free = free_fn;
     l->surrogate = block;
+}
+
+// what target.hip (fi_target.h) reads of a learner; the block itself is target.hip's
+int fi::learner_target_view(fi_learner* l, TargetView* out) {
+    FI_REQUIRE(l && out, "learner_target_view: null argument");
+    *out = TargetView{l->dev, l->T, l->B, l->A, l->comm ? l->nranks : 1, l->nparams, l->params, l->stream, l->target};
+    return FI_OK;
+}
+
+void fi::learner_set_target_block(fi_learner* l, TargetBlock* block, void (*free_fn)(void*)) {
+    l->target_free = free_fn;
+    l->target = block;
 }
 
 // ------------------------------------------------------------------ params

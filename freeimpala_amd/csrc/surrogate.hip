@@ -35,13 +35,13 @@
 #include "fi_surrogate.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "policy_row.h"  // pair_log_prob, policy_row_grad, adv_moments: shared with target.hip
 #include "row_stream.h"  // kCols, kWaves, load_run, store_run, wave_reduce, block_sums, tile_plan
 
 namespace fi {
 
 namespace {
 constexpr int kAhead = 8;  // time steps of the scan whose loads are in flight ahead of the chain
-constexpr int kStatThreads = 256;
 
 struct StatsBlock {
     uint64_t rows, rows_clipped;
@@ -75,21 +75,10 @@ struct SurArgs {
     uint32_t normalize;
 };
 
-// m and s of A from the scan's partials: thread i adds the partials i, i + 256, ... in ascending order,
-// then block_sums. The loss kernel's workgroups and the stats kernel run this same sequence on the same
-// numbers, so they hold the same bits. n = 1 gives s = 0 exactly: S2 / 1 and (S1 / 1)^2 are one product.
+// m and s of A from the scan's partials (policy_row.h): the loss kernel's workgroups and the stats kernel
+// run the same sequence on the same numbers, so they hold the same bits
 __device__ __forceinline__ void moments(const SurArgs& a, double* red, double& m, double& s) {
-    static_assert(kStatThreads == 64 * kWaves, "the loss and the stats kernel share this reduction");
-    double v[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < a.nscan; i += kStatThreads) {
-        v[0] += a.mom[2 * i];
-        v[1] += a.mom[2 * i + 1];
-    }
-    block_sums<2, kWaves>(v, red);
-    const double n = (double)a.T * (double)a.B;
-    const double m1 = v[0] / n, var = v[1] / n - m1 * m1;
-    m = *a.pivot + m1;
-    s = sqrt(var > 0.0 ? var : (var == var ? 0.0 : var));  // NaN stays NaN
+    adv_moments(a.mom, a.pivot, a.nscan, a.T, a.B, red, m, s);
 }
 
 }  // namespace
@@ -127,16 +116,7 @@ __global__ __launch_bounds__(64 * kWaves) void surrogate_rows_kernel(SurArgs a) 
             const float* __restrict__ zm = lm + (uint32_t)lane * S;
             if ((unsigned)at >= A) ++nbad;
             const uint32_t ai = at < 0 ? 0u : ((uint32_t)at >= A ? A - 1u : (uint32_t)at);
-            // x = {pi side, mu side}: one instruction sequence for both
-            f32x2 mx = {zp[0], zm[0]};
-            for (uint32_t i = 1; i < A; ++i) mx = __builtin_elementwise_max(mx, f32x2{zp[i], zm[i]});
-            f32x2 se = {0.f, 0.f};
-            for (uint32_t i = 0; i < A; ++i) {
-                const f32x2 x = (f32x2{zp[i], zm[i]} - mx) * L2E;
-                se += f32x2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-            }
-            const f32x2 lg = f32x2{__builtin_amdgcn_logf(se.x), __builtin_amdgcn_logf(se.y)} * LN2;
-            const f32x2 la = (f32x2{zp[ai], zm[ai]} - mx) - lg;  // log pi(a), log mu(a)
+            const f32x2 la = pair_log_prob(zp, zm, A, ai);  // log pi(a), log mu(a): one instruction sequence for both
             const float lr = la.x - la.y;
             const float rho = __expf(lr);
             const size_t e = (size_t)t * B + b0 + lane;
@@ -257,20 +237,7 @@ __global__ __launch_bounds__(64 * kWaves) void surrogate_loss_kernel(SurArgs a) 
             const bool clipped = (an > 0.f && rho > hi) || (an < 0.f && rho < lo);
             const float rc = fminf(fmaxf(rho, lo), hi);
             const float g = clipped ? 0.f : -rho * an;
-            float mx = z[0];
-            for (uint32_t i = 1; i < A; ++i) mx = fmaxf(mx, z[i]);
-            float se = 0.f, sed = 0.f;
-            for (uint32_t i = 0; i < A; ++i) {
-                const float d = z[i] - mx, e = __builtin_amdgcn_exp2f(d * L2E);
-                se += e;
-                sed += e * d;
-            }
-            const float lg = __builtin_amdgcn_logf(se) * LN2;
-            const float plogp = sed / se - lg;  // sum pi log pi
-            for (uint32_t i = 0; i < A; ++i) {
-                const float d = z[i] - mx, p = __builtin_amdgcn_exp2f(d * L2E) / se;
-                z[i] = g * ((i == ai ? 1.f : 0.f) - p) + ec * p * ((d - lg) - plogp);
-            }
+            const float plogp = policy_row_grad(z, A, ai, g, ec);  // sum pi log pi; z holds dlogits now
             const float td = v - vs;
             a.dval[(size_t)t * B + b0 + lane] = bc * td;
             sum[0] += (double)(-fminf(rho * an, rc * an));
@@ -338,7 +305,9 @@ Layout layout_of(int T, int B, const TilePlan& p) {
     return l;
 }
 
-int check_params(const std::string& who, const fi_surrogate_params* p) {
+}  // namespace
+
+int surrogate_check_params(const std::string& who, const fi_surrogate_params* p) {
     FI_REQUIRE(p, who + ": null params");
     FI_REQUIRE(std::isfinite(p->clip) && p->clip > 0.f, who + ": clip " + std::to_string(p->clip) + " must be finite and > 0");
     FI_REQUIRE(std::isfinite(p->adv_eps) && p->adv_eps >= 0.f,
@@ -346,7 +315,6 @@ int check_params(const std::string& who, const fi_surrogate_params* p) {
     FI_REQUIRE(p->normalize <= 1u, who + ": normalize " + std::to_string(p->normalize) + " is neither 0 nor 1");
     return FI_OK;
 }
-}  // namespace
 
 size_t surrogate_workspace_bytes(int T, int B, int A) {
     TilePlan p{};
@@ -358,11 +326,13 @@ int surrogate_loss_blocks(int T, int B, int A) {
     return tile_plan("surrogate", T, B, A, &p) == FI_OK ? p.ct * p.slices : 0;
 }
 
-int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
-                     const float* disc, const float* val, const fi_vtrace_hparams& hp, const fi_surrogate_params& prm,
-                     float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
-                     int* bad, hipStream_t stream, KernelTagger* tg, const double** partials, int* nblk_out) {
-    FI_REQUIRE(pi && mu && act && rew && disc && val && vs && adv && dlog && dval && ws, "surrogate: null argument");
+namespace {
+// What surrogate_launch and surrogate_front_launch share. prepare: every check, in one order and with one
+// set of messages, and the kernels' arguments over ws; nothing is enqueued and no attribute changed.
+// The front passes nullptr for dlog, dval, losses and stats, which it does not have.
+int prepare(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew, const float* disc,
+            const float* val, const fi_vtrace_hparams& hp, float* vs, float* adv, float* dlog, float* dval,
+            const double* losses, const void* stats, void* ws, size_t ws_bytes, int* bad, SurArgs* out) {
     TilePlan p{};
     FI_TRY(tile_plan("surrogate", T, B, A, &p));
     FI_REQUIRE((uintptr_t)pi % 16 == 0 && (uintptr_t)mu % 16 == 0 && (uintptr_t)dlog % 16 == 0,
@@ -385,27 +355,26 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
     a.d = (float*)w, a.k = (float*)(w + lay.row), a.lr = (float*)(w + 2 * lay.row);
     a.mom = (double*)(w + lay.mom), a.pivot = (double*)(w + lay.pivot), a.part = (double*)(w + lay.part);
     a.clipped = (unsigned long long*)(w + lay.clipped);
-    a.bad = bad;
+    a.bad = bad ? bad : (int*)(w + lay.bad);  // stand-alone: count into the workspace
     a.hp = hp;
-    a.clip = prm.clip, a.adv_eps = prm.adv_eps, a.normalize = prm.normalize;
-    if (!bad) {  // stand-alone: count into the workspace
-        a.bad = (int*)(w + lay.bad);
-        FI_HIP_CHECK(hipMemsetAsync(a.bad, 0, sizeof(int), stream));
-    }
-    const unsigned nblk = (unsigned)(p.ct * p.slices);
-    const size_t row_bytes = (size_t)kWaves * kCols * (A | 1) * sizeof(float), row_most = (size_t)kWaves * kCols * 65 * 4;
-    // more than 64 KB of dynamic LDS: A > 30 for the rows kernel, A = 63, 64 for the loss kernel
-    if (2 * row_bytes > 64 * 1024) {
+    *out = a;
+    return FI_OK;
+}
+
+size_t row_bytes_of(int A) { return (size_t)kWaves * kCols * (A | 1) * sizeof(float); }
+constexpr size_t kRowMost = (size_t)kWaves * kCols * 65 * 4;
+
+// the rows and scan kernels on prepared arguments; own_bad: the counter inside ws is zeroed first
+int launch_front(const SurArgs& a, bool own_bad, hipStream_t stream, KernelTagger* tg) {
+    if (own_bad) FI_HIP_CHECK(hipMemsetAsync(a.bad, 0, sizeof(int), stream));
+    const size_t row_bytes = row_bytes_of(a.A);
+    if (2 * row_bytes > 64 * 1024) {  // more than 64 KB of dynamic LDS: A > 30
         static std::atomic<uint64_t> raised{0};
-        FI_TRY(raise_lds((const void*)surrogate_rows_kernel, raised, 2 * row_most));
-    }
-    if (row_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        FI_TRY(raise_lds((const void*)surrogate_loss_kernel, raised, row_most));
+        FI_TRY(raise_lds((const void*)surrogate_rows_kernel, raised, 2 * kRowMost));
     }
     {
         TagScope t(tg, "surrogate_rows");
-        hipLaunchKernelGGL(surrogate_rows_kernel, dim3(nblk), dim3(64 * kWaves), 2 * row_bytes, stream, a);
+        hipLaunchKernelGGL(surrogate_rows_kernel, dim3((unsigned)(a.ct * a.slices)), dim3(64 * kWaves), 2 * row_bytes, stream, a);
         FI_HIP_CHECK(hipGetLastError());
     }
     {
@@ -413,6 +382,37 @@ int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, cons
         hipLaunchKernelGGL(surrogate_scan_kernel, dim3((unsigned)a.nscan), dim3(64), 0, stream, a);
         FI_HIP_CHECK(hipGetLastError());
     }
+    return FI_OK;
+}
+}  // namespace
+
+int surrogate_front_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                           const float* disc, const float* val, const fi_vtrace_hparams& hp, float* vs, float* adv, void* ws,
+                           size_t ws_bytes, int* bad, hipStream_t stream, KernelTagger* tg, SurrogateFront* out) {
+    FI_REQUIRE(pi && mu && act && rew && disc && val && vs && adv && ws && out, "surrogate: null argument");
+    SurArgs a{};
+    FI_TRY(prepare(T, B, A, pi, mu, act, rew, disc, val, hp, vs, adv, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, bad,
+                   &a));
+    FI_TRY(launch_front(a, !bad, stream, tg));
+    *out = SurrogateFront{a.lr, a.mom, a.pivot, a.bad, a.nscan, a.ct, a.slices, a.slice_len};
+    return FI_OK;
+}
+
+int surrogate_launch(int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                     const float* disc, const float* val, const fi_vtrace_hparams& hp, const fi_surrogate_params& prm,
+                     float* vs, float* adv, float* dlog, float* dval, double* losses, void* stats, void* ws, size_t ws_bytes,
+                     int* bad, hipStream_t stream, KernelTagger* tg, const double** partials, int* nblk_out) {
+    FI_REQUIRE(pi && mu && act && rew && disc && val && vs && adv && dlog && dval && ws, "surrogate: null argument");
+    SurArgs a{};
+    FI_TRY(prepare(T, B, A, pi, mu, act, rew, disc, val, hp, vs, adv, dlog, dval, losses, stats, ws, ws_bytes, bad, &a));
+    a.clip = prm.clip, a.adv_eps = prm.adv_eps, a.normalize = prm.normalize;
+    const size_t row_bytes = row_bytes_of(A);
+    if (row_bytes > 64 * 1024) {  // more than 64 KB of dynamic LDS: A = 63, 64
+        static std::atomic<uint64_t> raised{0};
+        FI_TRY(raise_lds((const void*)surrogate_loss_kernel, raised, kRowMost));
+    }
+    FI_TRY(launch_front(a, !bad, stream, tg));
+    const unsigned nblk = (unsigned)(a.ct * a.slices);
     {
         TagScope t(tg, "surrogate_loss");
         hipLaunchKernelGGL(surrogate_loss_kernel, dim3(nblk), dim3(64 * kWaves), row_bytes, stream, a);
@@ -478,7 +478,7 @@ using namespace fi;
 
 extern "C" int fi_surrogate_enable(fi_learner* l, const fi_surrogate_params* params) {
     FI_REQUIRE(l, "surrogate_enable: null learner");
-    FI_TRY(check_params("surrogate_enable", params));
+    FI_TRY(surrogate_check_params("surrogate_enable", params));
     SurrogateView v{};
     FI_TRY(learner_surrogate_view(l, &v));
     if (params->normalize && v.nranks > 1)
@@ -547,7 +547,7 @@ extern "C" int fi_surrogate_loss_fp32(int T, int B, int A, const float* pi, cons
                                       const fi_surrogate_params* params, float* vs, float* adv, float* dlogits, float* dvalue,
                                       double* losses, void* stats_dev, void* ws, size_t ws_bytes, int* bad, void* stream) {
     FI_REQUIRE(hp, "surrogate_loss: null hparams");
-    FI_TRY(check_params("surrogate_loss", params));
+    FI_TRY(surrogate_check_params("surrogate_loss", params));
     return surrogate_launch(T, B, A, pi, mu, act, rew, disc, val, *hp, *params, vs, adv, dlogits, dvalue, losses, stats_dev,
                             ws, ws_bytes, bad, (hipStream_t)stream, nullptr, nullptr, nullptr);
 }

@@ -325,6 +325,66 @@ class DeviceLearner:
         check(surrogate.lib().fi_surrogate_stats_dev(self._h, C.byref(p)), "fi_surrogate_stats_dev")
         return int(p.value)
 
+    # --- the target network (include/fi_target.h; the rule: freeimpala_amd/target.py)
+    def enable_target(self, period: int = 4, tau: float = 1.0) -> None:
+        """A slowly moving copy theta- of the parameters: a surrogate step takes V-trace's importance weights
+        against it and its trust region around it (IMPACT); every ``period``-th update moves theta- by ``tau``
+        towards the parameters (1.0: a copy). The first call copies the parameters; a later one replaces the two
+        numbers. Between any two steps."""
+        from . import target
+        prm = target.params(period, tau)
+        check(target.lib().fi_target_enable(self._h, C.byref(prm)), "fi_target_enable")
+
+    def disable_target(self) -> None:
+        """The next step is the plain surrogate (or V-trace) step again, bit for bit; theta- stays as it is."""
+        from . import target
+        check(target.lib().fi_target_disable(self._h), "fi_target_disable")
+
+    def sync_target(self) -> None:
+        """Enqueue theta- <- parameters now: after ``set_params`` / ``load_state``, which do not touch theta-."""
+        from . import target
+        check(target.lib().fi_target_sync(self._h), "fi_target_sync")
+
+    def target_state(self) -> dict:
+        """Wait for the stream and return enabled, period, tau and the block: updates, rows, mean_log_r,
+        mean_sq_log_r of the last target step."""
+        from . import target
+        prm, st, on = target.TargetParams(), target.TargetStats(), C.c_uint32()
+        check(target.lib().fi_target_get_state(self._h, C.byref(prm), C.byref(st), C.byref(on)), "fi_target_get_state")
+        return dict(enabled=bool(on.value), period=int(prm.period), tau=float(prm.tau), **st.as_dict())
+
+    def target_params(self) -> np.ndarray:
+        """theta- as fp32 (waits for the stream). Not part of ``save_state``: a checkpoint keeps it beside the blob,
+        and a resuming process calls ``enable_target``, ``set_target_params``, ``load_state``."""
+        from . import target
+        out = np.empty(self.param_count, np.float32)
+        check(target.lib().fi_target_get_params(self._h, out.ctypes.data, out.size), "fi_target_get_params")
+        return out
+
+    def set_target_params(self, p: np.ndarray) -> None:
+        from . import target
+        a = np.ascontiguousarray(p, np.float32).reshape(-1)
+        check(target.lib().fi_target_set_params(self._h, a.ctypes.data, a.size), "fi_target_set_params")
+
+    def _target_ptr(self, name: str) -> int:
+        from . import target
+        p = C.c_void_p()
+        check(getattr(target.lib(), name)(self._h, C.byref(p)), name)
+        return int(p.value)
+
+    def target_params_dev(self) -> int:
+        """The device address of theta- (fp32, ``param_count`` floats): what an evaluation actor reads through
+        ``set_params_ptr``."""
+        return self._target_ptr("fi_target_params_dev")
+
+    def target_logits_dev(self) -> int:
+        """The device address of the target logits (T + 1, B, A) of the last target step."""
+        return self._target_ptr("fi_target_logits_dev")
+
+    def target_stats_dev(self) -> int:
+        """The device address of the 32-byte block {uint64 updates, rows; double mean_log_r, mean_sq_log_r}."""
+        return self._target_ptr("fi_target_stats_dev")
+
     # --- parameters published on the device (include/fi_publish.h)
     def publish(self) -> int:
         """Enqueue a publication of the parameters as they are at this point of the learner's stream

@@ -39,6 +39,7 @@
 #include "fi_popart.h"
 #include "fi_publish.h"
 #include "fi_surrogate.h"
+#include "fi_target.h"
 #include "fi_train.h"
 
 namespace freeimpala_amd {
@@ -521,6 +522,37 @@ public:
     bool surrogate_state(size_t p, fi_surrogate_state& out) {
         if (p >= handles_.size()) return fail(0, "player_index out of range");
         if (fi_surrogate_get_state(handles_[p], &out) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    // The target network on player p (include/fi_target.h): a slowly moving copy of the parameters. A
+    // surrogate step takes V-trace's importance weights against it and its trust region around it; every
+    // period-th update moves it by tau towards the parameters. The copy is not in save_state()'s blob: a
+    // resuming process calls enable_target, fi_target_set_params on the handles, then load_state; a
+    // process that only wants the copy to follow a loaded state calls sync_target after the load.
+    bool enable_target(size_t p, uint32_t period = FI_TARGET_PERIOD, float tau = FI_TARGET_TAU) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const fi_target_params prm{period, tau, {0u, 0u}};
+        for (fi_learner* h : shards_[p])
+            if (fi_target_enable(h, &prm) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool disable_target(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_target_disable(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool sync_target(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_target_sync(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool target_state(size_t p, fi_target_params& params, fi_target_stats& stats, bool* enabled = nullptr) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        uint32_t on = 0;
+        if (fi_target_get_state(handles_[p], &params, &stats, &on) != FI_OK) return fail(p, fi_last_error());
+        if (enabled) *enabled = on != 0;
         return true;
     }
     // --starting-model resume (Model::loadFromDisk bytes + version).

@@ -57,6 +57,17 @@ reward clip with the clipped surrogate objective on the learner; `--normalize-ad
 Every window's entry of those runs carries the last step's clipped fraction and advantage moments; the output
 goes to profiles/train_breakout_surrogate.json unless --out names another file. The default, `--objective
 vtrace`, leaves the loops as they were.
+
+`--n-fresh K` (K divides B = 256, K < B) is the replaying loop: every unroll goes through an `EntryRing` of 8 B
+entries (`ring.push_rollout(actor)`), and the learner takes B / K steps per unroll, each
+`learner.step_ring(ring, n_fresh=K)`: K columns are that unroll's, B - K are drawn from the entries read before that
+are still resident, up to eight unrolls old. (The first unroll is one step with all B columns fresh: nothing can be
+replayed before something was read.) The learning-rate schedule runs over the steps taken. Next to `rmsprop` it runs
+`rmsprop_surrogate` with `--objective surrogate`, and with `--target-period P` (`--target-tau TAU`, default 1; both
+need `--objective surrogate`) also `rmsprop_surrogate_target`: the same with the learner's target network on
+(include/fi_target.h), whose windows carry mean_log_r and the target's updates. The output goes to
+profiles/train_breakout_target.json unless --out names another file. Without these flags the script runs the loops
+it ran before.
 """
 from __future__ import annotations
 
@@ -77,6 +88,8 @@ N, T, A, GAMMA, SEED, MAX_STEPS = 256, 20, 3, 0.99, 1, 1000
 RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
 POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configuration
 SURROGATE_CLIP = 0.2  # --clip EPS: the eps of the rmsprop_surrogate* configurations
+TARGET = None  # --target-period P, --target-tau TAU: (P, TAU) of the rmsprop_surrogate_target configuration
+RING_UNROLLS = 8  # --n-fresh: the ring holds this many unrolls
 
 
 def make_learner(config: str, unrolls: int) -> DeviceLearner:
@@ -91,6 +104,8 @@ def make_learner(config: str, unrolls: int) -> DeviceLearner:
             L.set_reward_clip(RMSPROP["reward_clip"])
         if "surrogate" in config:  # the second objective in V-trace's place; everything else as `rmsprop`
             L.set_objective("surrogate", clip=SURROGATE_CLIP, normalize_advantages=config.endswith("_normalized"))
+        if config.endswith("_target"):
+            L.enable_target(*TARGET)
         return L
     return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
 
@@ -105,8 +120,13 @@ def popart_window(L: DeviceLearner, config: str) -> dict:
     """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
     if "surrogate" in config:
         s = L.objective_state()
-        return dict(clipped_fraction=round(s["rows_clipped"] / max(1, s["rows"]), 4), adv_mean=round(s["adv_mean"], 6),
-                    adv_std=round(s["adv_std"], 6))
+        w = dict(clipped_fraction=round(s["rows_clipped"] / max(1, s["rows"]), 4), adv_mean=round(s["adv_mean"], 6),
+                 adv_std=round(s["adv_std"], 6))
+        if config.endswith("_target"):
+            t = L.target_state()
+            w.update(mean_log_r=round(t["mean_log_r"], 6), mean_sq_log_r=round(t["mean_sq_log_r"], 6),
+                     target_updates=t["updates"])
+        return w
     if config != "rmsprop_popart":
         return {}
     s = L.popart_state()
@@ -196,6 +216,43 @@ def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dic
                 learner_version=last.get("version"), train_state=state)
 
 
+def train_replay(config: str, unrolls: int, window: int, n_fresh: int, publish: str = "host", ex: dict | None = None) -> dict:
+    """--n-fresh K: every unroll through an entry ring, N / K steps per unroll with K fresh columns each."""
+    from freeimpala_amd.ring import EntryRing
+    per_unroll = N // n_fresh
+    L = make_learner(config, 1 + (unrolls - 1) * per_unroll)
+    a = Actor("atari", N, num_actions=A, seed=SEED)
+    hand_over(L, a, publish)
+    explore(a, ex)
+    a.begin_rollout(T)
+    ring = EntryRing(L.entry_bytes, RING_UNROLLS * N, seed=SEED)
+    e = breakout.BreakoutEnv(N, GAMMA, seed=SEED, max_steps=MAX_STEPS)
+    assert e.rollout(a, 1) == 1  # step 0 of the first unroll
+    curve, seen, last = [], e.stats(), {}
+    t0 = time.perf_counter()
+    for u in range(1, unrolls + 1):
+        assert e.rollout(a, T) == T
+        ring.push_rollout(a)
+        if u == 1:
+            last = L.step_ring(ring)  # all N fresh: there is nothing to replay yet
+        else:
+            for _ in range(per_unroll):
+                last = L.step_ring(ring, n_fresh=n_fresh)
+        hand_over(L, a, publish)
+        if u % window == 0:
+            seen, w = window_of(e, seen)
+            w.update(popart_window(L, config))
+            curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
+    wall = time.perf_counter() - t0
+    state = L.train_state()
+    a.sync()
+    a.end_rollout()
+    for h in (a, e, ring, L):
+        h.close()
+    return dict(curve=curve, wall_s=round(wall, 3), env_steps=unrolls * N * T, env_steps_per_s=round(unrolls * N * T / wall, 1),
+                learner_steps=1 + (unrolls - 1) * per_unroll, learner_version=last.get("version"), train_state=state)
+
+
 def untrained(window: int) -> dict:
     """One window of the loop with a never-stepped learner's parameters: no record, no learner step."""
     L = make_learner("adam", 1)
@@ -214,6 +271,22 @@ def untrained(window: int) -> dict:
     return w
 
 
+def default_out(args, explores: bool, default_mode: bool) -> str:
+    """The file under profiles/ a run without --out writes: every comparison keeps its own record. The replaying loop
+    and the target network come first, so that `--objective surrogate` with either leaves the surrogate's file alone."""
+    if args.n_fresh is not None or args.target_period is not None:
+        return "train_breakout_target.json"
+    if args.objective == "surrogate":
+        return "train_breakout_surrogate.json"
+    if args.popart is not None:
+        return "train_breakout_popart.json"
+    if args.diagnostics:
+        return "train_breakout_diag.json"
+    if explores:
+        return "train_breakout_explore.json"
+    return "train_breakout.json" if default_mode else "train_breakout_device_publish.json"
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -229,6 +302,9 @@ def main() -> None:
     ap.add_argument("--objective", choices=("vtrace", "surrogate"), default="vtrace")
     ap.add_argument("--clip", type=float, default=0.2, metavar="EPS")
     ap.add_argument("--normalize-adv", action="store_true")
+    ap.add_argument("--n-fresh", type=int, default=None, metavar="K")
+    ap.add_argument("--target-period", type=int, default=None, metavar="P")
+    ap.add_argument("--target-tau", type=float, default=1.0, metavar="TAU")
     args = ap.parse_args()
     if args.diagnostics < 0:
         raise SystemExit("train_breakout: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
@@ -253,29 +329,40 @@ def main() -> None:
             raise SystemExit("train_breakout: --clip EPS is the surrogate's clip range, finite and > 0")
         SURROGATE_CLIP = args.clip
         configs = ("rmsprop", "rmsprop_surrogate") + (("rmsprop_surrogate_normalized",) if args.normalize_adv else ())
-        if args.out is None:
-            args.out = os.path.join(ROOT, "profiles", "train_breakout_surrogate.json")
     elif args.normalize_adv or args.clip != 0.2:
         raise SystemExit("train_breakout: --clip and --normalize-adv belong to --objective surrogate")
-    if args.out is None and args.popart is not None:
-        args.out = os.path.join(ROOT, "profiles", "train_breakout_popart.json")
-    if args.out is None and args.diagnostics:
-        args.out = os.path.join(ROOT, "profiles", "train_breakout_diag.json")
-    if args.out is None and ex:
-        args.out = os.path.join(ROOT, "profiles", "train_breakout_explore.json")
+    global TARGET
+    if args.target_period is not None:
+        if args.objective != "surrogate":
+            raise SystemExit("train_breakout: --target-period needs --objective surrogate (the target network serves that objective)")
+        if args.target_period < 1 or not 0.0 < args.target_tau <= 1.0:
+            raise SystemExit("train_breakout: --target-period P >= 1, --target-tau TAU in (0, 1]")
+        TARGET = (args.target_period, args.target_tau)
+        configs += ("rmsprop_surrogate_target",)
+    elif args.target_tau != 1.0:
+        raise SystemExit("train_breakout: --target-tau belongs to --target-period")
+    if args.n_fresh is not None:
+        if not 1 <= args.n_fresh < N or N % args.n_fresh:
+            raise SystemExit(f"train_breakout: --n-fresh K divides the batch {N} and is smaller than it")
+        if args.overlap or args.diagnostics or args.popart is not None:
+            raise SystemExit("train_breakout: --n-fresh is a loop of its own; run --overlap, --diagnostics and --popart apart")
+        configs = tuple(c for c in configs if c != "adam")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "train_breakout.json" if default_mode else "train_breakout_device_publish.json")
+        args.out = os.path.join(ROOT, "profiles", default_out(args, bool(ex), default_mode))
     if hip.device_count() < 1:
         raise SystemExit("train_breakout: no HIP device; nothing is measured without one")
     t0 = time.perf_counter()
     base = untrained(args.window)
-    if args.overlap:
+    if args.n_fresh is not None:
+        runs = {c: train_replay(c, args.unrolls, args.window, args.n_fresh, args.publish, ex) for c in configs}
+    elif args.overlap:
         runs = {c: train_overlapped(c, args.unrolls, args.window, ex, args.diagnostics) for c in configs}
     else:
         runs = {c: train(c, args.unrolls, args.window, args.publish, ex, args.diagnostics) for c in configs}
     res = dict(what="learning measurement on an environment that needs the frame stack: the Atari policy on "
-                    "device-resident Breakout, mean score of the episodes finished in every window of unrolls; two "
-                    "documented settings, nothing tuned, no threshold",
+                    "device-resident Breakout, mean score of the episodes finished in every window of unrolls; " +
+                    ("two" if args.n_fresh is None else f"the replaying loop, {len(configs)}") +
+                    " documented settings, nothing tuned, no threshold",
                num_envs=N, batch=N, seq_len=T, num_actions=A, gamma=GAMMA, seed=SEED, max_steps=MAX_STEPS,
                unrolls=args.unrolls, window_unrolls=args.window, return_range=[0, MAX_STEPS],
                configs=dict(adam="Adam, fi_learner_config_init's rate and moments, global-norm clip 40",
@@ -297,6 +384,15 @@ def main() -> None:
             res["configs"][c] = dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)",
                                      objective=dict(name="surrogate", clip=args.clip, adv_eps=1e-8,
                                                     normalize_advantages=c.endswith("_normalized")))
+            if c.endswith("_target"):
+                res["configs"][c]["target"] = dict(period=TARGET[0], tau=TARGET[1])
+    if args.n_fresh is not None:
+        res["configs"].pop("adam", None)
+        steps = 1 + (args.unrolls - 1) * (N // args.n_fresh)
+        for c in res["configs"].values():
+            c["lr_steps"] = steps
+        res.update(replay=dict(n_fresh=args.n_fresh, steps_per_unroll=N // args.n_fresh, ring_entries=RING_UNROLLS * N,
+                               note="the first unroll is one step with every column fresh"))
     if ex:
         res.update(exploration=dict(ex, note="the training actors explore and record their behaviour logits as mu; "
                                              "the scores are the exploring actors' own; the untrained baseline is the plain draw"))
