@@ -7,7 +7,7 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/fi_*.h)
 
@@ -29,8 +29,8 @@ oracle:
 	$(MAKE) -s -C oracle
 
 # C++ host-side check programs, one per header of the C ABI and its C++ wrapper (tests/cpp/host_<name>_check.cpp):
-# learner (device_learner.hpp), actor, rollout, rollouts (fi_gather.h), ring, env, breakout, train, publish, explore, diag, popart, surrogate, target
-HOST_CHECKS := learner actor rollout rollouts ring env breakout train publish explore diag popart surrogate target
+# learner (device_learner.hpp), actor, rollout, rollouts (fi_gather.h), ring, env, breakout, train, publish, explore, diag, popart, surrogate, target, kl
+HOST_CHECKS := learner actor rollout rollouts ring env breakout train publish explore diag popart surrogate target kl
 HOST_CXX = g++ -std=c++17 -O2 -Wall -Wextra -Iinclude $< -o $@ -L$(LIBDIR) -lfi_learner -pthread '-Wl,-rpath,$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 host: $(HOST_CHECKS:%=build/host_%_check) build/replay_check build/host_util_check
 build/host_%_check: tests/cpp/host_%_check.cpp $(wildcard include/*.h include/freeimpala_amd/*.hpp) $(LIBDIR)/libfi_learner.so

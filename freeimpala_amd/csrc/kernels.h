@@ -9,6 +9,7 @@
 
 #include "fi_diag.h"
 #include "fi_gather.h"
+#include "fi_kl.h"
 #include "fi_learner.h"
 #include "fi_surrogate.h"
 
@@ -361,6 +362,30 @@ struct TargetView {
 };
 int learner_target_view(fi_learner* l, TargetView* out);
 void learner_set_target_block(fi_learner* l, TargetBlock* block, void (*free_fn)(void*));
+
+// learner.cpp: a learner's KL-penalty block (include/fi_kl.h, where the rule stands), made and freed by
+// kl.hip, which hands its launchers in with it: learner.cpp names nothing of kl.hip, so a library of the
+// learner alone links. While the block is `on` and the step has the reference's logits (mu always, tlogits
+// after a target forward), run_step calls `penalty` directly behind the objective's launches and `adapt`
+// behind the optimiser (and PopArt's and the target's updates)
+struct KlBlock {
+    void* state = nullptr;  // device, 48 bytes: fi_kl_stats
+    void* ws = nullptr;     // one fp64 partial per workgroup of the penalty kernel
+    size_t ws_bytes = 0;
+    bool on = false;
+    fi_kl_params prm{};  // by value into every later launch; prm.coeff: what fi_kl_enable was last given
+    int (*penalty)(const KlBlock*, int T, int B, int A, const float* pi, const float* q, float* dlog,
+                   hipStream_t stream) = nullptr;
+    int (*adapt)(const KlBlock*, int T, int B, int A, const int* skip, hipStream_t stream) = nullptr;
+};
+struct KlView {
+    int dev, T, B, A, nranks;
+    bool has_target;  // fi_target_enable was called on the handle
+    hipStream_t stream;
+    KlBlock* block;
+};
+int learner_kl_view(fi_learner* l, KlView* out);
+void learner_set_kl_block(fi_learner* l, KlBlock* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

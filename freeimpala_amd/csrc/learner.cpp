@@ -136,6 +136,9 @@ struct fi_learner {
     // the target network (fi_target.h): the block is target.hip's, with its launchers
     TargetBlock* target = nullptr;
     void (*target_free)(void*) = nullptr;
+    // the KL penalty (fi_kl.h): the block is kl.hip's, with its launchers
+    KlBlock* kl = nullptr;
+    void (*kl_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -239,6 +242,7 @@ static void destroy(fi_learner* l) {
     if (l->popart) l->popart_free(l->popart);
     if (l->surrogate) l->surrogate_free(l->surrogate);
     if (l->target) l->target_free(l->target);
+    if (l->kl) l->kl_free(l->kl);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -734,6 +738,16 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
                              l->bad));
         loss_part = vtrace_partials(l->vt_ws);
     }
+    // the KL penalty (fi_kl.h): c (pi - q) onto dlogits, q the batch's mu or this step's target logits; a
+    // step without the reference's logits enqueues neither this nor kl_adapt
+    const KlBlock* kb = l->kl && l->kl->on ? l->kl : nullptr;
+    const float* kl_q = !kb ? nullptr
+                            : (kb->prm.reference == FI_KL_REF_BEHAVIOUR ? l->mu
+                                                                        : (sur_on && tgt_on ? l->target->tlogits : nullptr));
+    if (kl_q) {
+        Tag t(l, "kl_penalty");
+        FI_TRY(kb->penalty(kb, l->T, l->B, l->A, l->logits, kl_q, l->dlogits, l->stream));
+    }
     if (l->popart) {  // d/dv -> d/dn: one division by sigma; row T (no gradient) is not touched
         Tag t(l, "popart_scale");
         FI_TRY(l->popart->scale(l->dvalue, (size_t)l->TB, l->popart->state, l->stream));
@@ -791,6 +805,11 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         // the target moves towards the parameters this update left; skipped with the update
         Tag t(l, "target_update");
         FI_TRY(l->target->update(l->target, l->params, l->bad, l->stream));
+    }
+    if (kl_q) {
+        // the coefficient moves on this step's mean KL; not when the update was skipped
+        Tag t(l, "kl_adapt");
+        FI_TRY(kb->adapt(kb, l->T, l->B, l->A, l->bad, l->stream));
     }
     if (l->atari) {
         Tag t(l, "weights_bf16");
@@ -1380,6 +1399,18 @@ int fi::learner_target_view(fi_learner* l, TargetView* out) {
 void fi::learner_set_target_block(fi_learner* l, TargetBlock* block, void (*free_fn)(void*)) {
     l->target_free = free_fn;
     l->target = block;
+}
+
+// what kl.hip (fi_kl.h) reads of a learner; the block itself is kl.hip's
+int fi::learner_kl_view(fi_learner* l, KlView* out) {
+    FI_REQUIRE(l && out, "learner_kl_view: null argument");
+    *out = KlView{l->dev, l->T, l->B, l->A, l->comm ? l->nranks : 1, l->target != nullptr, l->stream, l->kl};
+    return FI_OK;
+}
+
+void fi::learner_set_kl_block(fi_learner* l, KlBlock* block, void (*free_fn)(void*)) {
+    l->kl_free = free_fn;
+    l->kl = block;
 }
 
 // ------------------------------------------------------------------ params

@@ -1,8 +1,9 @@
-// policy_row.h -- the one copy of the per-row arithmetic of the surrogate objectives (surrogate.hip,
-// target.hip). Internal, header-only; one lane works on one row of A logits in the wave's padded LDS
-// rows (row_stream.h).
+// policy_row.h -- the one copy of the per-row arithmetic of the surrogate objectives and the KL penalty
+// (surrogate.hip, target.hip, kl.hip). Internal, header-only; one lane works on one row of A logits in the
+// wave's padded LDS rows (row_stream.h).
 //   pair_log_prob    log-softmax at the action of two rows from one instruction sequence: bit-equal rows
 //                    give bit-equal results, so their difference is exactly 0
+//   pair_kl_grad     KL(q || p) of two rows and its gradient c (p - q), written over the p row
 //   policy_row_grad  softmax, entropy and dlogits of one row, written over the row
 //   adv_moments      m and s of the advantages from the scan's fp64 partials, in one fixed order
 #pragma once
@@ -25,6 +26,28 @@ __device__ __forceinline__ f32x2 pair_log_prob(const float* __restrict__ zp, con
     }
     const f32x2 lg = f32x2{__builtin_amdgcn_logf(se.x), __builtin_amdgcn_logf(se.y)} * LN2;
     return (f32x2{zp[ai], zm[ai]} - mx) - lg;
+}
+
+// zp[j] <- c (p_j - q_j), p = softmax(zp), q = softmax(zq); returns KL(q || p) = sum_j q_j (log q_j - log p_j).
+// As in pair_log_prob both rows go through one instruction sequence: bit-equal rows give 0 everywhere, exactly
+__device__ __forceinline__ float pair_kl_grad(float* __restrict__ zp, const float* __restrict__ zq, uint32_t A, float c) {
+    f32x2 mx = {zp[0], zq[0]};
+    for (uint32_t i = 1; i < A; ++i) mx = __builtin_elementwise_max(mx, f32x2{zp[i], zq[i]});
+    f32x2 se = {0.f, 0.f};
+    for (uint32_t i = 0; i < A; ++i) {
+        const f32x2 x = (f32x2{zp[i], zq[i]} - mx) * L2E;
+        se += f32x2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+    }
+    const f32x2 lg = f32x2{__builtin_amdgcn_logf(se.x), __builtin_amdgcn_logf(se.y)} * LN2;
+    float kl = 0.f;
+    for (uint32_t i = 0; i < A; ++i) {
+        const f32x2 d = f32x2{zp[i], zq[i]} - mx, x = d * L2E;
+        const f32x2 p = f32x2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)} / se;
+        const f32x2 l = d - lg;  // log p_i, log q_i
+        kl += p.y * (l.y - l.x);
+        zp[i] = c * (p.x - p.y);
+    }
+    return kl;
 }
 
 // z[j] <- g (1[j = ai] - p_j) + ec p_j (log p_j - sum_k p_k log p_k), p = softmax(z); returns sum_k p_k log p_k

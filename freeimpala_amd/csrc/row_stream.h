@@ -1,9 +1,10 @@
-// row_stream.h -- what the loss-side streams over the logits share (diag.hip, surrogate.hip; the
-// reductions also vtrace.hip). Internal, header-only. The pattern: workgroup (c, s) owns the 64 columns
-// of column tile c and the time steps of slice s (tile_plan), its four waves the steps t .. t + 3 of a
-// round, lane = column. The rows of one (t, tile) are one contiguous run of nb * A floats in global
-// memory: load_run moves it, 16 bytes per lane and access, into the wave's padded LDS rows, then one
-// lane works per row; store_run is the way back. Row stride in LDS: A | 1 floats. ds_read_b32 is served
+// row_stream.h -- what the loss-side streams over the logits share (diag.hip, surrogate.hip, target.hip,
+// kl.hip; the reductions also vtrace.hip). Internal, header-only. The pattern: workgroup (c, s) owns the
+// 64 columns of column tile c and the time steps of slice s (tile_plan), its four waves the steps
+// t .. t + 3 of a round, lane = column. The rows of one (t, tile) are one contiguous run of nb * A floats
+// in global memory: load_run moves it, 16 bytes per lane and access, into the wave's padded LDS rows,
+// then one lane works per row; store_run is the way back, add_run the way onto a tensor that holds
+// values already (kl.hip). Row stride in LDS: A | 1 floats. ds_read_b32 is served
 // in two groups of 32 lanes over 32 banks, so a stride of A floats is a 2-way conflict at A = 18 and a
 // 32-way one at A = 64 in each group; an odd stride maps the 32 lanes of a group to 32 different banks.
 // A workgroup's fp64 sums are reduced per wave by DPP / permlane moves (wave_reduce) and over the waves
@@ -186,6 +187,52 @@ __device__ __forceinline__ void store_run(float* __restrict__ out, const float* 
     if ((uint32_t)lane < tail) {
         const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
         go[e] = lp[r * S + cc];
+    }
+}
+
+// store_run's traversal onto a tensor that holds values already: out[e] += the LDS row value. The
+// rows do not go through LDS a second time (kl.hip: a third padded row set does not fit a CU at A = 64):
+// a lane loads up to kPiecesPerLane of its 16-byte pieces together, adds and stores them. Each element of
+// the run is read once and written once, by the same lane; plain loads and stores, since out was written
+// by the launch in front and is read again by the one behind.
+__device__ __forceinline__ void add_run(float* __restrict__ out, const float* __restrict__ lp, uint32_t g0, uint32_t n,
+                                        uint32_t A, uint32_t S, int lane) {
+    const uint32_t to4 = (4u - (g0 & 3u)) & 3u, head = to4 < n ? to4 : n;
+    const uint32_t nbody = (n - head) >> 2, tail = n - head - 4u * nbody;
+    float* __restrict__ go = out + g0;
+    f32x4* __restrict__ go4 = (f32x4*)(go + head);
+    for (uint32_t k0 = 0; k0 < nbody; k0 += 64u * kPiecesPerLane) {
+        f32x4 v[kPiecesPerLane];
+#pragma unroll
+        for (int u = 0; u < kPiecesPerLane; ++u) {
+            const uint32_t p = k0 + 64u * u + lane;
+            if (p < nbody) v[u] = go4[p];
+        }
+#pragma unroll
+        for (int u = 0; u < kPiecesPerLane; ++u) {
+            const uint32_t p = k0 + 64u * u + lane;
+            if (p < nbody) {
+                const uint32_t e = head + 4u * p;
+                uint32_t r = e / A, cc = e - r * A;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[u][j] += lp[r * S + cc];
+                    if (++cc == A) {
+                        cc = 0u;
+                        ++r;
+                    }
+                }
+                go4[p] = v[u];
+            }
+        }
+    }
+    if ((uint32_t)lane < head) {
+        const uint32_t r = (uint32_t)lane / A, cc = (uint32_t)lane - r * A;
+        go[lane] += lp[r * S + cc];
+    }
+    if ((uint32_t)lane < tail) {
+        const uint32_t e = head + 4u * nbody + lane, r = e / A, cc = e - r * A;
+        go[e] += lp[r * S + cc];
     }
 }
 

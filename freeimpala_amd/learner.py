@@ -385,6 +385,45 @@ class DeviceLearner:
         """The device address of the 32-byte block {uint64 updates, rows; double mean_log_r, mean_sq_log_r}."""
         return self._target_ptr("fi_target_stats_dev")
 
+    # --- the adaptive KL penalty (include/fi_kl.h; the rule: freeimpala_amd/kl.py)
+    def enable_kl_penalty(self, reference: str = "behaviour", coeff: float = 1.0, kl_target: float = 0.01,
+                          adapt: bool = True, band: float = 1.5, factor: float = 2.0, coeff_min: float = 2.0 ** -20,
+                          coeff_max: float = 2.0 ** 20) -> None:
+        """Add coeff * KL(q || pi) to the loss, q the batch's behaviour policy ("behaviour") or the target network's
+        policy of the batch ("target": penalised are the surrogate steps that run a target forward). With ``adapt``
+        the coefficient doubles (``factor``) when a step's mean KL passes ``band * kl_target`` and halves below
+        ``kl_target / band``, on the device. A second call replaces the parameters and keeps the coefficient."""
+        from . import kl
+        if reference not in kl.REFERENCES:
+            raise ValueError(f"reference {reference!r}: one of {sorted(kl.REFERENCES)}")
+        prm = kl.params(reference, adapt, coeff, kl_target, band, factor, coeff_min, coeff_max)
+        check(kl.lib().fi_kl_enable(self._h, C.byref(prm)), "fi_kl_enable")
+
+    def disable_kl_penalty(self) -> None:
+        """The next step is the step without the penalty again, bit for bit; the block stays as it is."""
+        from . import kl
+        check(kl.lib().fi_kl_disable(self._h), "fi_kl_disable")
+
+    def set_kl_coeff(self, c: float) -> None:
+        """The coefficient <- c, behind the steps already enqueued (a resuming process: enable, this, load_state)."""
+        from . import kl
+        check(kl.lib().fi_kl_set_coeff(self._h, c), "fi_kl_set_coeff")
+
+    def kl_state(self) -> dict:
+        """Wait for the stream and return the parameters (reference, adapt, kl_target, band, factor, coeff_min,
+        coeff_max), enabled and the block: coeff, mean_kl, kl_sum, rows, updates, raised, lowered."""
+        from . import kl
+        prm, st, on = kl.KlParams(), kl.KlStats(), C.c_uint32()
+        check(kl.lib().fi_kl_get_state(self._h, C.byref(prm), C.byref(st), C.byref(on)), "fi_kl_get_state")
+        return dict(enabled=bool(on.value), **prm.as_dict(), **st.as_dict())
+
+    def kl_state_dev(self) -> int:
+        """The device address of the 48-byte block (freeimpala_amd.kl.unpack_state reads its bytes)."""
+        from . import kl
+        p = C.c_void_p()
+        check(kl.lib().fi_kl_state_dev(self._h, C.byref(p)), "fi_kl_state_dev")
+        return int(p.value)
+
     # --- parameters published on the device (include/fi_publish.h)
     def publish(self) -> int:
         """Enqueue a publication of the parameters as they are at this point of the learner's stream

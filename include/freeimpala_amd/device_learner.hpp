@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "fi_diag.h"
+#include "fi_kl.h"
 #include "fi_learner.h"
 #include "fi_popart.h"
 #include "fi_publish.h"
@@ -552,6 +553,40 @@ public:
         if (p >= handles_.size()) return fail(0, "player_index out of range");
         uint32_t on = 0;
         if (fi_target_get_state(handles_[p], &params, &stats, &on) != FI_OK) return fail(p, fi_last_error());
+        if (enabled) *enabled = on != 0;
+        return true;
+    }
+    // The adaptive KL penalty on player p (include/fi_kl.h): coeff * KL(q || pi) in the loss, q the batch's
+    // behaviour policy (FI_KL_REF_BEHAVIOUR) or the target network's (FI_KL_REF_TARGET, after enable_target);
+    // with adapt the coefficient moves on the device towards kl_target. With --data-parallel > 1 the handles
+    // share a communicator and adapt is refused (each shard would see its own mean); a fixed coefficient is
+    // fine. The block is not in save_state()'s blob: a resuming process calls enable_kl_penalty, set_kl_coeff,
+    // load_state.
+    bool enable_kl_penalty(size_t p, uint32_t reference = FI_KL_REF_BEHAVIOUR, float coeff = FI_KL_COEFF,
+                           float kl_target = FI_KL_TARGET, bool adapt = true, float band = FI_KL_BAND,
+                           float factor = FI_KL_FACTOR, float coeff_min = FI_KL_COEFF_MIN, float coeff_max = FI_KL_COEFF_MAX) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const fi_kl_params prm{reference, adapt ? 1u : 0u, coeff, kl_target, band, factor, coeff_min, coeff_max};
+        for (fi_learner* h : shards_[p])
+            if (fi_kl_enable(h, &prm) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool disable_kl_penalty(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_kl_disable(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool set_kl_coeff(size_t p, double c) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_kl_set_coeff(h, c) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool kl_state(size_t p, fi_kl_params& params, fi_kl_stats& stats, bool* enabled = nullptr) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        uint32_t on = 0;
+        if (fi_kl_get_state(handles_[p], &params, &stats, &on) != FI_OK) return fail(p, fi_last_error());
         if (enabled) *enabled = on != 0;
         return true;
     }

@@ -68,6 +68,13 @@ need `--objective surrogate`) also `rmsprop_surrogate_target`: the same with the
 (include/fi_target.h), whose windows carry mean_log_r and the target's updates. The output goes to
 profiles/train_breakout_target.json unless --out names another file. Without these flags the script runs the loops
 it ran before.
+
+`--kl-coeff C` (include/fi_kl.h; `--kl-target D`, default 0.01; `--kl-reference behaviour|target`, default behaviour;
+`--kl-fixed` keeps C where it is) runs, next to the configurations the other flags select, the last of them once more
+with the KL penalty on the learner, as `<that configuration>_kl`: C KL(q || pi) in the loss, q the records' behaviour
+policy or (with `--target-period`) the target network's, and C adapting to D on the device. Every window's entry of
+that run carries the coefficient, the last step's mean KL and the counts of adaptations, and the same go to stderr
+with the window's score. The output goes to profiles/train_breakout_kl.json unless --out names another file.
 """
 from __future__ import annotations
 
@@ -88,11 +95,13 @@ N, T, A, GAMMA, SEED, MAX_STEPS = 256, 20, 3, 0.99, 1, 1000
 RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
 POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configuration
 SURROGATE_CLIP = 0.2  # --clip EPS: the eps of the rmsprop_surrogate* configurations
+KL = None  # --kl-coeff C, --kl-target D, --kl-reference R, --kl-fixed: enable_kl_penalty's arguments of the *_kl configuration
 TARGET = None  # --target-period P, --target-tau TAU: (P, TAU) of the rmsprop_surrogate_target configuration
 RING_UNROLLS = 8  # --n-fresh: the ring holds this many unrolls
 
 
 def make_learner(config: str, unrolls: int) -> DeviceLearner:
+    kl_on, config = config.endswith("_kl"), config.removesuffix("_kl")
     if config.startswith("rmsprop"):
         L = DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", optimizer="rmsprop",
                           lr=RMSPROP["lr"], seed=SEED)
@@ -106,6 +115,8 @@ def make_learner(config: str, unrolls: int) -> DeviceLearner:
             L.set_objective("surrogate", clip=SURROGATE_CLIP, normalize_advantages=config.endswith("_normalized"))
         if config.endswith("_target"):
             L.enable_target(*TARGET)
+        if kl_on:  # behind enable_target: the reference "target" needs the target network
+            L.enable_kl_penalty(**KL)
         return L
     return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
 
@@ -116,8 +127,15 @@ def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
     return now, dict(episodes=n, mean_return=round(s / n, 4) if n else None)
 
 
-def popart_window(L: DeviceLearner, config: str) -> dict:
+def popart_window(L: DeviceLearner, config: str, mean_return=None) -> dict:
     """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
+    if config.endswith("_kl"):
+        w = popart_window(L, config.removesuffix("_kl"))
+        k = L.kl_state()
+        w.update(kl_coeff=k["coeff"], mean_kl=round(k["mean_kl"], 6), kl_raised=k["raised"], kl_lowered=k["lowered"])
+        print(f"[{config}] mean_return {mean_return} kl_coeff {k['coeff']:g} mean_kl {k['mean_kl']:.6f} "
+              f"raised {k['raised']} lowered {k['lowered']}", file=sys.stderr, flush=True)
+        return w
     if "surrogate" in config:
         s = L.objective_state()
         w = dict(clipped_fraction=round(s["rows_clipped"] / max(1, s["rows"]), 4), adv_mean=round(s["adv_mean"], 6),
@@ -170,7 +188,7 @@ def train_overlapped(config: str, unrolls: int, window: int, ex: dict | None = N
             last = L.wait()
             bv = L.batch_versions
             seen, w = window_of(e, seen)
-            w.update(popart_window(L, config))
+            w.update(popart_window(L, config, w["mean_return"]))
             pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4),
                               batch_versions=[bv["min"], bv["max"], round(bv["mean"], 3)], **w))
@@ -203,7 +221,7 @@ def train(config: str, unrolls: int, window: int, publish: str = "host", ex: dic
         hand_over(L, a, publish)
         if u % window == 0:
             seen, w = window_of(e, seen)
-            w.update(popart_window(L, config))
+            w.update(popart_window(L, config, w["mean_return"]))
             pending = diag.report(L, config, pending, w)
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
     wall = time.perf_counter() - t0
@@ -241,7 +259,7 @@ def train_replay(config: str, unrolls: int, window: int, n_fresh: int, publish: 
         hand_over(L, a, publish)
         if u % window == 0:
             seen, w = window_of(e, seen)
-            w.update(popart_window(L, config))
+            w.update(popart_window(L, config, w["mean_return"]))
             curve.append(dict(unroll=u, total_loss=round(last["total_loss"], 4), grad_norm=round(last["grad_norm"], 4), **w))
     wall = time.perf_counter() - t0
     state = L.train_state()
@@ -273,7 +291,10 @@ def untrained(window: int) -> dict:
 
 def default_out(args, explores: bool, default_mode: bool) -> str:
     """The file under profiles/ a run without --out writes: every comparison keeps its own record. The replaying loop
-    and the target network come first, so that `--objective surrogate` with either leaves the surrogate's file alone."""
+    and the target network come first, so that `--objective surrogate` with either leaves the surrogate's file alone;
+    the KL penalty, the newest, in front of both. (getattr: a caller's Namespace may be older than the option.)"""
+    if getattr(args, "kl_coeff", None) is not None:
+        return "train_breakout_kl.json"
     if args.n_fresh is not None or args.target_period is not None:
         return "train_breakout_target.json"
     if args.objective == "surrogate":
@@ -287,7 +308,7 @@ def default_out(args, explores: bool, default_mode: bool) -> str:
     return "train_breakout.json" if default_mode else "train_breakout_device_publish.json"
 
 
-def main() -> None:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--unrolls", type=int, default=2000)
@@ -305,7 +326,15 @@ def main() -> None:
     ap.add_argument("--n-fresh", type=int, default=None, metavar="K")
     ap.add_argument("--target-period", type=int, default=None, metavar="P")
     ap.add_argument("--target-tau", type=float, default=1.0, metavar="TAU")
-    args = ap.parse_args()
+    ap.add_argument("--kl-coeff", type=float, default=None, metavar="C")
+    ap.add_argument("--kl-target", type=float, default=0.01, metavar="D")
+    ap.add_argument("--kl-reference", choices=("behaviour", "target"), default="behaviour")
+    ap.add_argument("--kl-fixed", action="store_true")
+    return ap
+
+
+def main() -> None:
+    args = parser().parse_args()
     if args.diagnostics < 0:
         raise SystemExit("train_breakout: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
     if args.overlap and args.publish != "device":
@@ -341,6 +370,16 @@ def main() -> None:
         configs += ("rmsprop_surrogate_target",)
     elif args.target_tau != 1.0:
         raise SystemExit("train_breakout: --target-tau belongs to --target-period")
+    global KL
+    if args.kl_coeff is not None:
+        if not 0.0 <= args.kl_coeff < float("inf") or not 0.0 < args.kl_target < float("inf"):
+            raise SystemExit("train_breakout: --kl-coeff C is finite and >= 0, --kl-target D finite and > 0")
+        if args.kl_reference == "target" and args.target_period is None:
+            raise SystemExit("train_breakout: --kl-reference target needs --target-period (the target network is the reference)")
+        KL = dict(reference=args.kl_reference, coeff=args.kl_coeff, kl_target=args.kl_target, adapt=not args.kl_fixed)
+        configs += (configs[-1] + "_kl",)
+    elif args.kl_fixed or args.kl_target != 0.01 or args.kl_reference != "behaviour":
+        raise SystemExit("train_breakout: --kl-target, --kl-reference and --kl-fixed belong to --kl-coeff")
     if args.n_fresh is not None:
         if not 1 <= args.n_fresh < N or N % args.n_fresh:
             raise SystemExit(f"train_breakout: --n-fresh K divides the batch {N} and is smaller than it")
@@ -383,9 +422,13 @@ def main() -> None:
         for c in configs[1:]:
             res["configs"][c] = dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)",
                                      objective=dict(name="surrogate", clip=args.clip, adv_eps=1e-8,
-                                                    normalize_advantages=c.endswith("_normalized")))
-            if c.endswith("_target"):
+                                                    normalize_advantages="_normalized" in c))
+            if "_target" in c:
                 res["configs"][c]["target"] = dict(period=TARGET[0], tau=TARGET[1])
+    if KL is not None:
+        c = configs[-1]
+        res["configs"][c] = dict(res["configs"].get(c) or res["configs"][c.removesuffix("_kl")],
+                                 kl=dict(KL, band=1.5, factor=2.0, coeff_min=2.0 ** -20, coeff_max=2.0 ** 20))
     if args.n_fresh is not None:
         res["configs"].pop("adam", None)
         steps = 1 + (args.unrolls - 1) * (N // args.n_fresh)
