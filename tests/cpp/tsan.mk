@@ -15,7 +15,7 @@ DEVOBJS := $(patsubst %,build/obj/%.hip.o,farmer vtrace gemm_f32 misc atari atar
 TSAN_LINK := -pthread -L$(TLIB) -lfi_learner '-Wl,-rpath,$$ORIGIN/lib' -Wl,-rpath,/opt/rocm/lib
 HDRS := $(wildcard include/freeimpala_amd/*.hpp) include/fi_learner.h $(TLIB)/libfi_learner.so
 
-all: build/tsan/host_learner_check build/tsan/fi_freeimpala asan
+all: build/tsan/host_learner_check build/tsan/fi_freeimpala build/tsan/tsan_gpu_probe asan
 
 build/tsan/learner.cpp.o: $(CSRC)/learner.cpp $(wildcard $(CSRC)/*.h) include/fi_learner.h
 	@mkdir -p build/tsan
@@ -32,6 +32,11 @@ build/tsan/host_learner_check: tests/cpp/host_learner_check.cpp $(HDRS)
 build/tsan/fi_freeimpala: tools/fi_freeimpala.cpp tools/cli_common.hpp $(HDRS)
 	@mkdir -p build/tsan
 	$(CLANGXX) -std=c++17 -O1 -g -fsanitize=thread -Iinclude $< -o $@ $(TSAN_LINK)
+
+# Whether the ROCm runtime starts in a TSAN process at all on this machine (the test asks first).
+build/tsan/tsan_gpu_probe: tests/cpp/tsan_gpu_probe.cpp
+	@mkdir -p build/tsan
+	$(CLANGXX) -std=c++17 -O1 -g -fsanitize=thread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $< -o $@ -pthread -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 
 # The same two programs and the library's host side under AddressSanitizer + UBSan (host-only
 # instrumentation again; tests/test_sanitizers.py runs them on the GPU with leak checking off,
