@@ -7,7 +7,7 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/vmpo.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/fi_*.h)
 
@@ -16,6 +16,12 @@ all: $(LIBDIR)/libfi_learner.so oracle host tools
 $(OBJDIR)/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# vmpo.hip: no packed fp32 instructions (v_pk_add_f32 and its kin) in its code object. With them the compiler
+# vectorises weight_of over the four advantages of a 16-byte piece in vmpo_sums_kernel alone, and the e of a row
+# there would no longer come from the instruction sequence that forms it in vmpo_loss_kernel (one lane per row):
+# fi_vmpo.h 3. and DESIGN.md 2.2 state one sequence for both. vmpo.hip also pins weight_of's contraction in the source
+$(OBJDIR)/vmpo.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -12,6 +12,7 @@
 #include "fi_kl.h"
 #include "fi_learner.h"
 #include "fi_surrogate.h"
+#include "fi_vmpo.h"
 
 namespace fi {
 
@@ -386,6 +387,34 @@ struct KlView {
 };
 int learner_kl_view(fi_learner* l, KlView* out);
 void learner_set_kl_block(fi_learner* l, KlBlock* block, void (*free_fn)(void*));
+
+// learner.cpp: a learner's V-MPO block (include/fi_vmpo.h, where the rule stands), made and freed by vmpo.hip,
+// which hands its launchers in with it: learner.cpp names nothing of vmpo.hip, so a library of the learner
+// alone links. While the block is `on`, run_step calls `launch` where it launches V-trace -- pi: the
+// learner's logits; front_pi: the logits the targets are taken on, the target network's behind a target
+// forward, else pi -- hands *partials, *nblk to grad_sqnorm and calls `eta` behind the optimiser (and
+// PopArt's, the target's and the KL penalty's updates)
+struct VmpoBlock {
+    void* state = nullptr;     // device, 88 bytes: fi_vmpo_state
+    void* ws = nullptr;        // histograms, selection words, partials
+    void* front_ws = nullptr;  // a surrogate workspace: the rows and scan kernels'
+    size_t ws_bytes = 0, front_bytes = 0;
+    bool on = false;
+    fi_vmpo_params prm{};  // by value into every later launch; prm.eta_init: what the block was made with
+    int (*launch)(const VmpoBlock*, int T, int B, int A, const float* pi, const float* front_pi, const float* mu,
+                  const int32_t* act, const float* rew, const float* disc, const float* val, const fi_vtrace_hparams& hp,
+                  float* vs, float* adv, float* dlog, float* dval, int* bad, hipStream_t stream, KernelTagger* tg,
+                  const double** partials, int* nblk) = nullptr;
+    int (*eta)(const VmpoBlock*, const int* skip, hipStream_t stream) = nullptr;
+};
+struct VmpoView {
+    int dev, T, B, A, nranks;
+    hipStream_t stream;
+    VmpoBlock* block;
+    SurrogateBlock* surrogate;  // nullable: fi_vmpo_enable turns it off, as fi_surrogate_enable turns `block` off
+};
+int learner_vmpo_view(fi_learner* l, VmpoView* out);
+void learner_set_vmpo_block(fi_learner* l, VmpoBlock* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

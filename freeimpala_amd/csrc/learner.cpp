@@ -139,6 +139,9 @@ struct fi_learner {
     // the KL penalty (fi_kl.h): the block is kl.hip's, with its launchers
     KlBlock* kl = nullptr;
     void (*kl_free)(void*) = nullptr;
+    // the V-MPO objective (fi_vmpo.h): the block is vmpo.hip's, with its launchers
+    VmpoBlock* vmpo = nullptr;
+    void (*vmpo_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -243,6 +246,7 @@ static void destroy(fi_learner* l) {
     if (l->surrogate) l->surrogate_free(l->surrogate);
     if (l->target) l->target_free(l->target);
     if (l->kl) l->kl_free(l->kl);
+    if (l->vmpo) l->vmpo_free(l->vmpo);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -683,6 +687,10 @@ static int target_forward(fi_learner* l) {
 }
 
 static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
+    // fi_vmpo.h: the selection is over the whole batch; a communicator attached after fi_vmpo_enable is caught here
+    if (l->vmpo && l->vmpo->on && l->comm && l->nranks > 1)
+        return fail(FI_ERR_STATE, "step: the V-MPO objective is on and the handle is attached to a communicator of " +
+                                      std::to_string(l->nranks) + " ranks; each rank would select from its own shard");
     const bool sync = out != nullptr || l->profiling;
     l->tag_used = 0;
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_a, l->stream));
@@ -704,7 +712,9 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     }
     mark(l, FI_PHASE_FORWARD);
     const bool sur_on = l->surrogate && l->surrogate->on, tgt_on = l->target && l->target->on;
-    if (sur_on && tgt_on) FI_TRY(target_forward(l));
+    const bool vmpo_on = l->vmpo && l->vmpo->on;  // fi_vmpo_enable and fi_surrogate_enable turn the other off
+    const bool tgt_fwd = (sur_on || vmpo_on) && tgt_on;
+    if (tgt_fwd) FI_TRY(target_forward(l));
     if (l->cfg.arch == FI_ARCH_MLP) FI_TRY(mlp_forward(l, l->params, l->logits, l->values));
     else {
         LearnerTagger tg(l);
@@ -723,6 +733,13 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         FI_TRY(l->target->launch(l->target, l->surrogate, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc,
                                  l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue, l->bad, l->stream,
                                  l->profiling ? &tg : nullptr, &loss_part, &vt_nblk));
+    } else if (vmpo_on) {
+        // the third objective (fi_vmpo.h): the targets on the target logits when there are any, the loss on
+        // the learner's own
+        LearnerTagger tg(l);
+        FI_TRY(l->vmpo->launch(l->vmpo, l->T, l->B, l->A, l->logits, tgt_on ? l->target->tlogits : l->logits, l->mu, l->act,
+                               l->rew, l->disc, l->values, l->cfg.hp, l->vs, l->pg_adv, l->dlogits, l->dvalue, l->bad,
+                               l->stream, l->profiling ? &tg : nullptr, &loss_part, &vt_nblk));
     } else if (sur_on) {
         // the second objective (fi_surrogate.h) in V-trace's place: the same outputs, its own tags
         LearnerTagger tg(l);
@@ -743,7 +760,7 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     const KlBlock* kb = l->kl && l->kl->on ? l->kl : nullptr;
     const float* kl_q = !kb ? nullptr
                             : (kb->prm.reference == FI_KL_REF_BEHAVIOUR ? l->mu
-                                                                        : (sur_on && tgt_on ? l->target->tlogits : nullptr));
+                                                                        : (tgt_fwd ? l->target->tlogits : nullptr));
     if (kl_q) {
         Tag t(l, "kl_penalty");
         FI_TRY(kb->penalty(kb, l->T, l->B, l->A, l->logits, kl_q, l->dlogits, l->stream));
@@ -810,6 +827,11 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
         // the coefficient moves on this step's mean KL; not when the update was skipped
         Tag t(l, "kl_adapt");
         FI_TRY(kb->adapt(kb, l->T, l->B, l->A, l->bad, l->stream));
+    }
+    if (vmpo_on) {
+        // the temperature's Adam step on this step's d_eta; not when the update was skipped
+        Tag t(l, "vmpo_eta");
+        FI_TRY(l->vmpo->eta(l->vmpo, l->bad, l->stream));
     }
     if (l->atari) {
         Tag t(l, "weights_bf16");
@@ -1406,6 +1428,18 @@ int fi::learner_kl_view(fi_learner* l, KlView* out) {
     FI_REQUIRE(l && out, "learner_kl_view: null argument");
     *out = KlView{l->dev, l->T, l->B, l->A, l->comm ? l->nranks : 1, l->target != nullptr, l->stream, l->kl};
     return FI_OK;
+}
+
+// what vmpo.hip (fi_vmpo.h) reads of a learner; the block itself is vmpo.hip's
+int fi::learner_vmpo_view(fi_learner* l, VmpoView* out) {
+    FI_REQUIRE(l && out, "learner_vmpo_view: null argument");
+    *out = VmpoView{l->dev, l->T, l->B, l->A, l->comm ? l->nranks : 1, l->stream, l->vmpo, l->surrogate};
+    return FI_OK;
+}
+
+void fi::learner_set_vmpo_block(fi_learner* l, VmpoBlock* block, void (*free_fn)(void*)) {
+    l->vmpo_free = free_fn;
+    l->vmpo = block;
 }
 
 void fi::learner_set_kl_block(fi_learner* l, KlBlock* block, void (*free_fn)(void*)) {

@@ -1,10 +1,10 @@
 // policy_row.h -- the one copy of the per-row arithmetic of the surrogate objectives and the KL penalty
-// (surrogate.hip, target.hip, kl.hip). Internal, header-only; one lane works on one row of A logits in the
+// (surrogate.hip, target.hip, kl.hip, vmpo.hip). Internal, header-only; one lane works on one row of A logits in the
 // wave's padded LDS rows (row_stream.h).
 //   pair_log_prob    log-softmax at the action of two rows from one instruction sequence: bit-equal rows
 //                    give bit-equal results, so their difference is exactly 0
 //   pair_kl_grad     KL(q || p) of two rows and its gradient c (p - q), written over the p row
-//   policy_row_grad  softmax, entropy and dlogits of one row, written over the row
+//   policy_row_grad  softmax, entropy and dlogits of one row, written over the row (_t<true>: also log p(a), vmpo.hip)
 //   adv_moments      m and s of the advantages from the scan's fp64 partials, in one fixed order
 #pragma once
 
@@ -50,8 +50,12 @@ __device__ __forceinline__ float pair_kl_grad(float* __restrict__ zp, const floa
     return kl;
 }
 
-// z[j] <- g (1[j = ai] - p_j) + ec p_j (log p_j - sum_k p_k log p_k), p = softmax(z); returns sum_k p_k log p_k
-__device__ __forceinline__ float policy_row_grad(float* __restrict__ z, uint32_t A, uint32_t ai, float g, float ec) {
+// z[j] <- g (1[j = ai] - p_j) + ec p_j (log p_j - sum_k p_k log p_k), p = softmax(z); returns sum_k p_k log p_k.
+// kLogp: *logp = log p_ai as well (vmpo.hip's weighted likelihood needs it; the ratio objectives have it
+// from pair_log_prob)
+template <bool kLogp>
+__device__ __forceinline__ float policy_row_grad_t(float* __restrict__ z, uint32_t A, uint32_t ai, float g, float ec,
+                                                   float* logp) {
     float mx = z[0];
     for (uint32_t i = 1; i < A; ++i) mx = fmaxf(mx, z[i]);
     float se = 0.f, sed = 0.f;
@@ -62,11 +66,15 @@ __device__ __forceinline__ float policy_row_grad(float* __restrict__ z, uint32_t
     }
     const float lg = __builtin_amdgcn_logf(se) * LN2;
     const float plogp = sed / se - lg;  // sum pi log pi
+    if (kLogp) *logp = (z[ai] - mx) - lg;
     for (uint32_t i = 0; i < A; ++i) {
         const float d = z[i] - mx, p = __builtin_amdgcn_exp2f(d * L2E) / se;
         z[i] = g * ((i == ai ? 1.f : 0.f) - p) + ec * p * ((d - lg) - plogp);
     }
     return plogp;
+}
+__device__ __forceinline__ float policy_row_grad(float* __restrict__ z, uint32_t A, uint32_t ai, float g, float ec) {
+    return policy_row_grad_t<false>(z, A, ai, g, ec, nullptr);
 }
 
 // m and s of A over n = T * B rows from the scan's partials mom[nscan][2] (sums of A - pivot and of its

@@ -494,6 +494,9 @@ extern "C" int fi_surrogate_enable(fi_learner* l, const fi_surrogate_params* par
     b->normalize = params->normalize;
     b->adv_eps = params->adv_eps;
     b->on = true;
+    VmpoView vm{};  // one objective at a time (fi_vmpo.h)
+    FI_TRY(learner_vmpo_view(l, &vm));
+    if (vm.block) vm.block->on = false;
     return FI_OK;
 }
 

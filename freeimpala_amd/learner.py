@@ -294,29 +294,62 @@ class DeviceLearner:
 
     # --- the learner's objective (include/fi_surrogate.h; the rule: freeimpala_amd/surrogate.py)
     def set_objective(self, name: str = "vtrace", clip: float = 0.2, normalize_advantages: bool = False,
-                      adv_eps: float = 1e-8) -> None:
+                      adv_eps: float = 1e-8, top_fraction: float = 0.5, eps_eta: float = 0.01, lr_eta: float = 1e-3,
+                      eta_init: float = 1.0, eta_min: float = 1e-8, adapt: bool = True) -> None:
         """"surrogate": every later step runs the clipped surrogate -min(rho A, clip(rho, 1 - clip, 1 + clip) A)
         on V-trace's targets in place of the V-trace policy gradient, with the advantages normalised over the
-        batch when asked; a second call replaces the numbers. "vtrace": the V-trace step again, bit for bit.
-        Between any two steps."""
-        from . import surrogate
+        batch when asked; a second call replaces the numbers. "vmpo" (include/fi_vmpo.h; the rule:
+        freeimpala_amd/vmpo.py): weighted maximum likelihood on the top ``top_fraction`` of the batch's advantages
+        with softmax(A / eta) weights, eta learned on the device (``eps_eta``, ``lr_eta``; ``eta_init`` when the
+        block is first made). One objective at a time. "vtrace": the V-trace step again, bit for bit. Between any
+        two steps."""
+        from . import surrogate, vmpo
         if name == "vtrace":
             check(surrogate.lib().fi_surrogate_disable(self._h), "fi_surrogate_disable")
+            check(vmpo.lib().fi_vmpo_disable(self._h), "fi_vmpo_disable")
         elif name == "surrogate":
             prm = surrogate.params(clip, normalize_advantages, adv_eps)
             check(surrogate.lib().fi_surrogate_enable(self._h, C.byref(prm)), "fi_surrogate_enable")
+        elif name == "vmpo":
+            prm = vmpo.params(top_fraction, eps_eta, eta_init, eta_min, lr_eta, adapt)
+            check(vmpo.lib().fi_vmpo_enable(self._h, C.byref(prm)), "fi_vmpo_enable")
         else:
-            raise ValueError(f"objective: vtrace | surrogate, not {name!r}")
+            raise ValueError(f"objective: vtrace | surrogate | vmpo, not {name!r}")
 
     def objective_state(self) -> dict:
-        """Wait for the stream and return objective ("vtrace" | "surrogate"), clip, normalize, adv_eps and the
-        last surrogate step's stats block: rows, rows_clipped, adv_mean, adv_std."""
-        from . import surrogate
+        """Wait for the stream and return objective ("vtrace" | "surrogate" | "vmpo"), clip, normalize, adv_eps and
+        the last surrogate step's stats block: rows, rows_clipped, adv_mean, adv_std (V-MPO's block: vmpo_state)."""
+        from . import surrogate, vmpo
         st = surrogate.SurrogateState()
         check(surrogate.lib().fi_surrogate_get_state(self._h, C.byref(st)), "fi_surrogate_get_state")
         d = st.as_dict()
-        d["objective"] = "surrogate" if d.pop("enabled") else "vtrace"
+        on = C.c_uint32()
+        check(vmpo.lib().fi_vmpo_get_state(self._h, None, None, C.byref(on)), "fi_vmpo_get_state")
+        d["objective"] = "surrogate" if d.pop("enabled") else ("vmpo" if on.value else "vtrace")
         return d
+
+    # --- the V-MPO objective's block (include/fi_vmpo.h)
+    def vmpo_state(self) -> dict:
+        """Wait for the stream and return enabled, the parameters (top_fraction, eps_eta, eta_init, eta_min, lr_eta,
+        adapt) and the block: eta, m1, m2, updates, rows, selected, threshold, adv_max, loss_eta, d_eta, sum_e,
+        sum_ea. Before the first set_objective("vmpo"): the defaults and a zero block."""
+        from . import vmpo
+        prm, st, on = vmpo.VmpoParams(), vmpo.VmpoState(), C.c_uint32()
+        check(vmpo.lib().fi_vmpo_get_state(self._h, C.byref(prm), C.byref(st), C.byref(on)), "fi_vmpo_get_state")
+        return dict(enabled=bool(on.value), **prm.as_dict(), **st.as_dict())
+
+    def set_vmpo_eta(self, eta: float) -> None:
+        """The temperature <- eta, behind the steps already enqueued (a resuming process: set_objective("vmpo"),
+        this, load_state)."""
+        from . import vmpo
+        check(vmpo.lib().fi_vmpo_set_eta(self._h, eta), "fi_vmpo_set_eta")
+
+    def vmpo_state_dev(self) -> int:
+        """The device address of the 88-byte block (freeimpala_amd.vmpo.unpack_state reads its bytes)."""
+        from . import vmpo
+        p = C.c_void_p()
+        check(vmpo.lib().fi_vmpo_state_dev(self._h, C.byref(p)), "fi_vmpo_state_dev")
+        return int(p.value)
 
     def surrogate_stats_ptr(self) -> int:
         """The device address of the 32-byte block {uint64 rows, rows_clipped; double adv_mean, adv_std}."""

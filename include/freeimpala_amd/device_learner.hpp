@@ -40,6 +40,7 @@
 #include "fi_popart.h"
 #include "fi_publish.h"
 #include "fi_surrogate.h"
+#include "fi_vmpo.h"
 #include "fi_target.h"
 #include "fi_train.h"
 
@@ -523,6 +524,33 @@ public:
     bool surrogate_state(size_t p, fi_surrogate_state& out) {
         if (p >= handles_.size()) return fail(0, "player_index out of range");
         if (fi_surrogate_get_state(handles_[p], &out) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    // The V-MPO objective on player p (include/fi_vmpo.h): weighted maximum likelihood on the top fraction of
+    // the batch's advantages, weights softmax(A / eta), eta learned on the device, until clear_vmpo(). It takes
+    // the surrogate's place (and set_surrogate takes its). With --data-parallel > 1 it is refused: the selection
+    // is over the whole batch. The block is not in save_state()'s blob: a resuming process calls set_vmpo,
+    // fi_vmpo_set_eta, load_state.
+    bool set_vmpo(size_t p, float top_fraction = FI_VMPO_TOP_FRACTION, float eps_eta = FI_VMPO_EPS_ETA,
+                  float lr_eta = FI_VMPO_LR_ETA, float eta_init = FI_VMPO_ETA_INIT, bool adapt = true,
+                  float eta_min = FI_VMPO_ETA_MIN) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const fi_vmpo_params prm{top_fraction, eps_eta, eta_init, eta_min, lr_eta, adapt ? 1u : 0u, {0u, 0u}};
+        for (fi_learner* h : shards_[p])
+            if (fi_vmpo_enable(h, &prm) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool clear_vmpo(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_vmpo_disable(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool vmpo_state(size_t p, fi_vmpo_params& params, fi_vmpo_state& state, bool* enabled = nullptr) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        uint32_t on = 0;
+        if (fi_vmpo_get_state(handles_[p], &params, &state, &on) != FI_OK) return fail(p, fi_last_error());
+        if (enabled) *enabled = on != 0;
         return true;
     }
     // The target network on player p (include/fi_target.h): a slowly moving copy of the parameters. A

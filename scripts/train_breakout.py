@@ -75,6 +75,14 @@ with the KL penalty on the learner, as `<that configuration>_kl`: C KL(q || pi) 
 policy or (with `--target-period`) the target network's, and C adapting to D on the device. Every window's entry of
 that run carries the coefficient, the last step's mean KL and the counts of adaptations, and the same go to stderr
 with the window's score. The output goes to profiles/train_breakout_kl.json unless --out names another file.
+
+`--objective vmpo` (include/fi_vmpo.h; `--vmpo-eps-eta EPS`, default 0.01; `--vmpo-lr-eta LR`, default 1e-3) runs,
+next to `rmsprop`, `rmsprop_vmpo`: the same numbers, schedule and reward clip with the V-MPO objective on the learner
+(the top half of the batch's advantages, weights softmax(A / eta), eta learned on the device), and with
+`--target-period P` also `rmsprop_vmpo_target`, whose targets are taken on the target network's logits; `--kl-coeff C
+--kl-reference target` then adds `rmsprop_vmpo_target_kl`, V-MPO's trust region. Every window's entry of those runs
+carries eta, the selected fraction, loss_eta and eta's updates, and eta goes to stderr with the window's score. The
+output goes to profiles/train_breakout_vmpo.json unless --out names another file.
 """
 from __future__ import annotations
 
@@ -96,6 +104,7 @@ RMSPROP = dict(lr=4.8e-4, decay=0.99, eps=0.01, momentum=0.0, reward_clip=1.0)
 POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configuration
 SURROGATE_CLIP = 0.2  # --clip EPS: the eps of the rmsprop_surrogate* configurations
 KL = None  # --kl-coeff C, --kl-target D, --kl-reference R, --kl-fixed: enable_kl_penalty's arguments of the *_kl configuration
+VMPO = None  # --vmpo-eps-eta EPS, --vmpo-lr-eta LR: set_objective("vmpo")'s arguments of the rmsprop_vmpo* configurations
 TARGET = None  # --target-period P, --target-tau TAU: (P, TAU) of the rmsprop_surrogate_target configuration
 RING_UNROLLS = 8  # --n-fresh: the ring holds this many unrolls
 
@@ -113,6 +122,8 @@ def make_learner(config: str, unrolls: int) -> DeviceLearner:
             L.set_reward_clip(RMSPROP["reward_clip"])
         if "surrogate" in config:  # the second objective in V-trace's place; everything else as `rmsprop`
             L.set_objective("surrogate", clip=SURROGATE_CLIP, normalize_advantages=config.endswith("_normalized"))
+        if "vmpo" in config:  # the third objective in V-trace's place; everything else as `rmsprop`
+            L.set_objective("vmpo", **VMPO)
         if config.endswith("_target"):
             L.enable_target(*TARGET)
         if kl_on:  # behind enable_target: the reference "target" needs the target network
@@ -130,12 +141,18 @@ def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
 def popart_window(L: DeviceLearner, config: str, mean_return=None) -> dict:
     """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
     if config.endswith("_kl"):
-        w = popart_window(L, config.removesuffix("_kl"))
+        w = popart_window(L, config.removesuffix("_kl"), mean_return)
         k = L.kl_state()
         w.update(kl_coeff=k["coeff"], mean_kl=round(k["mean_kl"], 6), kl_raised=k["raised"], kl_lowered=k["lowered"])
         print(f"[{config}] mean_return {mean_return} kl_coeff {k['coeff']:g} mean_kl {k['mean_kl']:.6f} "
               f"raised {k['raised']} lowered {k['lowered']}", file=sys.stderr, flush=True)
         return w
+    if "vmpo" in config:
+        v = L.vmpo_state()
+        print(f"[{config}] mean_return {mean_return} eta {v['eta']:g} selected {v['selected']}/{v['rows']} "
+              f"loss_eta {v['loss_eta']:.6f}", file=sys.stderr, flush=True)
+        return dict(eta=v["eta"], selected_fraction=round(v["selected"] / max(1, v["rows"]), 4), loss_eta=round(v["loss_eta"], 6),
+                    d_eta=round(v["d_eta"], 6), eta_updates=v["updates"])
     if "surrogate" in config:
         s = L.objective_state()
         w = dict(clipped_fraction=round(s["rows_clipped"] / max(1, s["rows"]), 4), adv_mean=round(s["adv_mean"], 6),
@@ -293,6 +310,8 @@ def default_out(args, explores: bool, default_mode: bool) -> str:
     """The file under profiles/ a run without --out writes: every comparison keeps its own record. The replaying loop
     and the target network come first, so that `--objective surrogate` with either leaves the surrogate's file alone;
     the KL penalty, the newest, in front of both. (getattr: a caller's Namespace may be older than the option.)"""
+    if args.objective == "vmpo":
+        return "train_breakout_vmpo.json"
     if getattr(args, "kl_coeff", None) is not None:
         return "train_breakout_kl.json"
     if args.n_fresh is not None or args.target_period is not None:
@@ -320,7 +339,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--epsilon-alpha", type=float, default=None)
     ap.add_argument("--diagnostics", type=int, default=0, metavar="K")
     ap.add_argument("--popart", type=float, nargs="?", const=3e-4, default=None, metavar="BETA")
-    ap.add_argument("--objective", choices=("vtrace", "surrogate"), default="vtrace")
+    ap.add_argument("--objective", choices=("vtrace", "surrogate", "vmpo"), default="vtrace")
+    ap.add_argument("--vmpo-eps-eta", type=float, default=0.01, metavar="EPS")
+    ap.add_argument("--vmpo-lr-eta", type=float, default=1e-3, metavar="LR")
     ap.add_argument("--clip", type=float, default=0.2, metavar="EPS")
     ap.add_argument("--normalize-adv", action="store_true")
     ap.add_argument("--n-fresh", type=int, default=None, metavar="K")
@@ -360,14 +381,24 @@ def main() -> None:
         configs = ("rmsprop", "rmsprop_surrogate") + (("rmsprop_surrogate_normalized",) if args.normalize_adv else ())
     elif args.normalize_adv or args.clip != 0.2:
         raise SystemExit("train_breakout: --clip and --normalize-adv belong to --objective surrogate")
+    global VMPO
+    if args.objective == "vmpo":
+        if args.popart is not None:
+            raise SystemExit("train_breakout: --objective vmpo and --popart are separate comparisons; run them apart")
+        if not 0.0 < args.vmpo_eps_eta < float("inf") or not 0.0 <= args.vmpo_lr_eta < float("inf"):
+            raise SystemExit("train_breakout: --vmpo-eps-eta EPS is finite and > 0, --vmpo-lr-eta LR finite and >= 0")
+        VMPO = dict(eps_eta=args.vmpo_eps_eta, lr_eta=args.vmpo_lr_eta)
+        configs = ("rmsprop", "rmsprop_vmpo")
+    elif args.vmpo_eps_eta != 0.01 or args.vmpo_lr_eta != 1e-3:
+        raise SystemExit("train_breakout: --vmpo-eps-eta and --vmpo-lr-eta belong to --objective vmpo")
     global TARGET
     if args.target_period is not None:
-        if args.objective != "surrogate":
-            raise SystemExit("train_breakout: --target-period needs --objective surrogate (the target network serves that objective)")
+        if args.objective == "vtrace":
+            raise SystemExit("train_breakout: --target-period needs --objective surrogate or vmpo (the target network serves those objectives)")
         if args.target_period < 1 or not 0.0 < args.target_tau <= 1.0:
             raise SystemExit("train_breakout: --target-period P >= 1, --target-tau TAU in (0, 1]")
         TARGET = (args.target_period, args.target_tau)
-        configs += ("rmsprop_surrogate_target",)
+        configs += ("rmsprop_" + args.objective + "_target",)
     elif args.target_tau != 1.0:
         raise SystemExit("train_breakout: --target-tau belongs to --target-period")
     global KL
@@ -423,6 +454,15 @@ def main() -> None:
             res["configs"][c] = dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)",
                                      objective=dict(name="surrogate", clip=args.clip, adv_eps=1e-8,
                                                     normalize_advantages="_normalized" in c))
+            if "_target" in c:
+                res["configs"][c]["target"] = dict(period=TARGET[0], tau=TARGET[1])
+    if args.objective == "vmpo":
+        res["configs"].pop("adam", None)
+        for c in configs[1:]:
+            if c.endswith("_kl"):
+                continue
+            res["configs"][c] = dict(RMSPROP, lr_end=0.0, lr_steps=args.unrolls, max_grad_norm="default (40)",
+                                     objective=dict(name="vmpo", top_fraction=0.5, eta_init=1.0, eta_min=1e-8, **VMPO))
             if "_target" in c:
                 res["configs"][c]["target"] = dict(period=TARGET[0], tau=TARGET[1])
     if KL is not None:
