@@ -12,6 +12,7 @@
 #include "fi_kl.h"
 #include "fi_learner.h"
 #include "fi_surrogate.h"
+#include "fi_upgo.h"
 #include "fi_vmpo.h"
 
 namespace fi {
@@ -415,6 +416,28 @@ struct VmpoView {
 };
 int learner_vmpo_view(fi_learner* l, VmpoView* out);
 void learner_set_vmpo_block(fi_learner* l, VmpoBlock* block, void (*free_fn)(void*));
+
+// learner.cpp: a learner's UPGO block (include/fi_upgo.h, where the rule stands), made and freed by upgo.hip,
+// which hands its launcher in with it: learner.cpp names nothing of upgo.hip, so a library of the learner
+// alone links. While the block is `on`, run_step calls `launch` behind the objective's launches and the KL
+// penalty's: the scan, the term onto dlog and the finalize. pi and mu: the learner's logits and the batch's
+// behaviour logits under every objective
+struct UpgoBlock {
+    void* state = nullptr;  // device, 40 bytes: fi_upgo_stats
+    void* ws = nullptr;     // AU and the partials
+    size_t ws_bytes = 0;
+    bool on = false;
+    fi_upgo_params prm{};  // by value into every later launch
+    int (*launch)(const UpgoBlock*, int T, int B, int A, const float* pi, const float* mu, const int32_t* act, const float* rew,
+                  const float* disc, const float* val, float* dlog, hipStream_t stream, KernelTagger* tg) = nullptr;
+};
+struct UpgoView {
+    int dev, T, B, A;
+    hipStream_t stream;
+    UpgoBlock* block;
+};
+int learner_upgo_view(fi_learner* l, UpgoView* out);
+void learner_set_upgo_block(fi_learner* l, UpgoBlock* block, void (*free_fn)(void*));
 
 // actor.hip: what fi_ring_push_rollout (ring.hip) compares with the ring, what fi_env_rollout
 // (env.hip) enqueues behind, and what fi_actor_set_params_dev (publish.hip) compares with the learner

@@ -142,6 +142,9 @@ struct fi_learner {
     // the V-MPO objective (fi_vmpo.h): the block is vmpo.hip's, with its launchers
     VmpoBlock* vmpo = nullptr;
     void (*vmpo_free)(void*) = nullptr;
+    // the UPGO term (fi_upgo.h): the block is upgo.hip's, with its launcher
+    UpgoBlock* upgo = nullptr;
+    void (*upgo_free)(void*) = nullptr;
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -247,6 +250,7 @@ static void destroy(fi_learner* l) {
     if (l->target) l->target_free(l->target);
     if (l->kl) l->kl_free(l->kl);
     if (l->vmpo) l->vmpo_free(l->vmpo);
+    if (l->upgo) l->upgo_free(l->upgo);
     if (l->comm) ncclCommDestroy(l->comm);
     for (hipEvent_t e : l->bucket_ev) hipEventDestroy(e);
     if (l->entries_consumed) hipEventDestroy(l->entries_consumed);
@@ -764,6 +768,13 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     if (kl_q) {
         Tag t(l, "kl_penalty");
         FI_TRY(kb->penalty(kb, l->T, l->B, l->A, l->logits, kl_q, l->dlogits, l->stream));
+    }
+    if (l->upgo && l->upgo->on) {
+        // the upgoing policy update (fi_upgo.h): coeff rho AU (pi - [a]) onto dlogits under any objective, on the
+        // learner's own logits and the batch's mu; tags upgo_scan, upgo_grad, upgo_finalize
+        LearnerTagger tg(l);
+        FI_TRY(l->upgo->launch(l->upgo, l->T, l->B, l->A, l->logits, l->mu, l->act, l->rew, l->disc, l->values, l->dlogits,
+                               l->stream, l->profiling ? &tg : nullptr));
     }
     if (l->popart) {  // d/dv -> d/dn: one division by sigma; row T (no gradient) is not touched
         Tag t(l, "popart_scale");
@@ -1440,6 +1451,18 @@ int fi::learner_vmpo_view(fi_learner* l, VmpoView* out) {
 void fi::learner_set_vmpo_block(fi_learner* l, VmpoBlock* block, void (*free_fn)(void*)) {
     l->vmpo_free = free_fn;
     l->vmpo = block;
+}
+
+// what upgo.hip (fi_upgo.h) reads of a learner; the block itself is upgo.hip's
+int fi::learner_upgo_view(fi_learner* l, UpgoView* out) {
+    FI_REQUIRE(l && out, "learner_upgo_view: null argument");
+    *out = UpgoView{l->dev, l->T, l->B, l->A, l->stream, l->upgo};
+    return FI_OK;
+}
+
+void fi::learner_set_upgo_block(fi_learner* l, UpgoBlock* block, void (*free_fn)(void*)) {
+    l->upgo_free = free_fn;
+    l->upgo = block;
 }
 
 void fi::learner_set_kl_block(fi_learner* l, KlBlock* block, void (*free_fn)(void*)) {

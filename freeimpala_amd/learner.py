@@ -457,6 +457,35 @@ class DeviceLearner:
         check(kl.lib().fi_kl_state_dev(self._h, C.byref(p)), "fi_kl_state_dev")
         return int(p.value)
 
+    # --- the upgoing policy update (include/fi_upgo.h; the rule: freeimpala_amd/upgo.py)
+    def enable_upgo(self, coeff: float = 1.0, rho_bar: float = 1.0) -> None:
+        """Add AlphaStar's UPGO term to the policy gradient, under any objective: coeff rho AU (pi - [a]) onto dlogits,
+        AU the upgoing return minus V, rho = min(rho_bar, pi(a) / mu(a)) on the learner's own logits and the batch's
+        mu. A second call replaces the two numbers."""
+        from . import upgo
+        prm = upgo.params(coeff, rho_bar)
+        check(upgo.lib().fi_upgo_enable(self._h, C.byref(prm)), "fi_upgo_enable")
+
+    def disable_upgo(self) -> None:
+        """The next step is the step without the term again, bit for bit; the block stays as it is."""
+        from . import upgo
+        check(upgo.lib().fi_upgo_disable(self._h), "fi_upgo_disable")
+
+    def upgo_state(self) -> dict:
+        """Wait for the stream and return coeff, rho_bar, enabled and the last step's block: loss_u, sum_au, rows,
+        links_up, rows_positive."""
+        from . import upgo
+        prm, st, on = upgo.UpgoParams(), upgo.UpgoStats(), C.c_uint32()
+        check(upgo.lib().fi_upgo_get_state(self._h, C.byref(prm), C.byref(st), C.byref(on)), "fi_upgo_get_state")
+        return dict(enabled=bool(on.value), **prm.as_dict(), **st.as_dict())
+
+    def upgo_state_dev(self) -> int:
+        """The device address of the 40-byte block (freeimpala_amd.upgo.unpack_state reads its bytes)."""
+        from . import upgo
+        p = C.c_void_p()
+        check(upgo.lib().fi_upgo_state_dev(self._h, C.byref(p)), "fi_upgo_state_dev")
+        return int(p.value)
+
     # --- parameters published on the device (include/fi_publish.h)
     def publish(self) -> int:
         """Enqueue a publication of the parameters as they are at this point of the learner's stream

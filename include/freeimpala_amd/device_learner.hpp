@@ -42,6 +42,7 @@
 #include "fi_surrogate.h"
 #include "fi_vmpo.h"
 #include "fi_target.h"
+#include "fi_upgo.h"
 #include "fi_train.h"
 
 namespace freeimpala_amd {
@@ -615,6 +616,30 @@ public:
         if (p >= handles_.size()) return fail(0, "player_index out of range");
         uint32_t on = 0;
         if (fi_kl_get_state(handles_[p], &params, &stats, &on) != FI_OK) return fail(p, fi_last_error());
+        if (enabled) *enabled = on != 0;
+        return true;
+    }
+    // The upgoing policy update on player p (include/fi_upgo.h): AlphaStar's UPGO term added onto the policy
+    // gradient under any objective, coeff rho AU (pi - [a]) with rho = min(rho_bar, pi(a) / mu(a)). It needs no
+    // statistic of the batch, so it is accepted with --data-parallel > 1 too; upgo_state reports the first
+    // shard's block. The block is not in save_state()'s blob: a resuming process calls enable_upgo again.
+    bool enable_upgo(size_t p, float coeff = FI_UPGO_COEFF, float rho_bar = FI_UPGO_RHO_BAR) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        const fi_upgo_params prm{coeff, rho_bar};
+        for (fi_learner* h : shards_[p])
+            if (fi_upgo_enable(h, &prm) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool disable_upgo(size_t p) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_upgo_disable(h) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    bool upgo_state(size_t p, fi_upgo_params& params, fi_upgo_stats& stats, bool* enabled = nullptr) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        uint32_t on = 0;
+        if (fi_upgo_get_state(handles_[p], &params, &stats, &on) != FI_OK) return fail(p, fi_last_error());
         if (enabled) *enabled = on != 0;
         return true;
     }

@@ -83,6 +83,12 @@ next to `rmsprop`, `rmsprop_vmpo`: the same numbers, schedule and reward clip wi
 --kl-reference target` then adds `rmsprop_vmpo_target_kl`, V-MPO's trust region. Every window's entry of those runs
 carries eta, the selected fraction, loss_eta and eta's updates, and eta goes to stderr with the window's score. The
 output goes to profiles/train_breakout_vmpo.json unless --out names another file.
+
+`--upgo-coeff C` (include/fi_upgo.h; `--upgo-rho-bar R`, default 1) runs, next to the configurations the other flags
+select, the last of them once more with AlphaStar's UPGO term on the learner, as `<that configuration>_upgo`. Every
+window's entry of that run carries the last step's share of links that are up, its share of rows with AU > 0 and its
+mean AU, and the same go to stderr with the window's score. The output goes to profiles/train_breakout_upgo.json unless
+--out names another file.
 """
 from __future__ import annotations
 
@@ -105,11 +111,13 @@ POPART_BETA = None  # --popart [BETA]: the beta of the rmsprop_popart configurat
 SURROGATE_CLIP = 0.2  # --clip EPS: the eps of the rmsprop_surrogate* configurations
 KL = None  # --kl-coeff C, --kl-target D, --kl-reference R, --kl-fixed: enable_kl_penalty's arguments of the *_kl configuration
 VMPO = None  # --vmpo-eps-eta EPS, --vmpo-lr-eta LR: set_objective("vmpo")'s arguments of the rmsprop_vmpo* configurations
+UPGO = None  # --upgo-coeff C, --upgo-rho-bar R: enable_upgo's arguments of the *_upgo configuration
 TARGET = None  # --target-period P, --target-tau TAU: (P, TAU) of the rmsprop_surrogate_target configuration
 RING_UNROLLS = 8  # --n-fresh: the ring holds this many unrolls
 
 
 def make_learner(config: str, unrolls: int) -> DeviceLearner:
+    upgo_on, config = config.endswith("_upgo"), config.removesuffix("_upgo")
     kl_on, config = config.endswith("_kl"), config.removesuffix("_kl")
     if config.startswith("rmsprop"):
         L = DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", optimizer="rmsprop",
@@ -128,6 +136,8 @@ def make_learner(config: str, unrolls: int) -> DeviceLearner:
             L.enable_target(*TARGET)
         if kl_on:  # behind enable_target: the reference "target" needs the target network
             L.enable_kl_penalty(**KL)
+        if upgo_on:
+            L.enable_upgo(**UPGO)
         return L
     return DeviceLearner("atari", seq_len=T, batch=N, num_actions=A, records="planes", seed=SEED)
 
@@ -140,6 +150,15 @@ def window_of(e: breakout.BreakoutEnv, before: dict) -> tuple[dict, dict]:
 
 def popart_window(L: DeviceLearner, config: str, mean_return=None) -> dict:
     """The statistics at a window's end (waits for the learner's stream); nothing for a plain configuration."""
+    if config.endswith("_upgo"):
+        w = popart_window(L, config.removesuffix("_upgo"), mean_return)
+        u = L.upgo_state()
+        rows = max(1, u["rows"])
+        w.update(links_up_fraction=round(u["links_up"] / rows, 4), au_positive_fraction=round(u["rows_positive"] / rows, 4),
+                 mean_au=round(u["sum_au"] / rows, 6))
+        print(f"[{config}] mean_return {mean_return} links_up {u['links_up']}/{u['rows']} AU > 0 {u['rows_positive']} "
+              f"mean AU {u['sum_au'] / rows:.6f}", file=sys.stderr, flush=True)
+        return w
     if config.endswith("_kl"):
         w = popart_window(L, config.removesuffix("_kl"), mean_return)
         k = L.kl_state()
@@ -309,7 +328,10 @@ def untrained(window: int) -> dict:
 def default_out(args, explores: bool, default_mode: bool) -> str:
     """The file under profiles/ a run without --out writes: every comparison keeps its own record. The replaying loop
     and the target network come first, so that `--objective surrogate` with either leaves the surrogate's file alone;
-    the KL penalty, the newest, in front of both. (getattr: a caller's Namespace may be older than the option.)"""
+    the KL penalty in front of both, the UPGO term, the newest, in front of all. (getattr: a caller's Namespace may be
+    older than the option.)"""
+    if getattr(args, "upgo_coeff", None) is not None:
+        return "train_breakout_upgo.json"
     if args.objective == "vmpo":
         return "train_breakout_vmpo.json"
     if getattr(args, "kl_coeff", None) is not None:
@@ -351,6 +373,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--kl-target", type=float, default=0.01, metavar="D")
     ap.add_argument("--kl-reference", choices=("behaviour", "target"), default="behaviour")
     ap.add_argument("--kl-fixed", action="store_true")
+    ap.add_argument("--upgo-coeff", type=float, default=None, metavar="C")
+    ap.add_argument("--upgo-rho-bar", type=float, default=1.0, metavar="R")
     return ap
 
 
@@ -411,6 +435,14 @@ def main() -> None:
         configs += (configs[-1] + "_kl",)
     elif args.kl_fixed or args.kl_target != 0.01 or args.kl_reference != "behaviour":
         raise SystemExit("train_breakout: --kl-target, --kl-reference and --kl-fixed belong to --kl-coeff")
+    global UPGO
+    if args.upgo_coeff is not None:
+        if not 0.0 <= args.upgo_coeff < float("inf") or not 0.0 < args.upgo_rho_bar < float("inf"):
+            raise SystemExit("train_breakout: --upgo-coeff C is finite and >= 0, --upgo-rho-bar R finite and > 0")
+        UPGO = dict(coeff=args.upgo_coeff, rho_bar=args.upgo_rho_bar)
+        configs += (configs[-1] + "_upgo",)
+    elif args.upgo_rho_bar != 1.0:
+        raise SystemExit("train_breakout: --upgo-rho-bar belongs to --upgo-coeff")
     if args.n_fresh is not None:
         if not 1 <= args.n_fresh < N or N % args.n_fresh:
             raise SystemExit(f"train_breakout: --n-fresh K divides the batch {N} and is smaller than it")
@@ -469,6 +501,9 @@ def main() -> None:
         c = configs[-1]
         res["configs"][c] = dict(res["configs"].get(c) or res["configs"][c.removesuffix("_kl")],
                                  kl=dict(KL, band=1.5, factor=2.0, coeff_min=2.0 ** -20, coeff_max=2.0 ** 20))
+    if UPGO is not None:
+        c = configs[-1]
+        res["configs"][c] = dict(res["configs"][c.removesuffix("_upgo")], upgo=UPGO)
     if args.n_fresh is not None:
         res["configs"].pop("adam", None)
         steps = 1 + (args.unrolls - 1) * (N // args.n_fresh)
