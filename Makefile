@@ -7,7 +7,7 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/vmpo.hip $(CSRC)/upgo.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/vmpo.hip $(CSRC)/upgo.hip $(CSRC)/mlp_bf16.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/fi_*.h)
 
@@ -25,6 +25,9 @@ $(OBJDIR)/vmpo.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-o
 
 # upgo.hip: the same switch; its cross-lane scan composes (k, d) pairs and nothing in it gains from packed fp32
 $(OBJDIR)/upgo.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
+# mlp_bf16.hip: the same switch; its fp32 work is MFMA accumulation and scalar epilogues
+$(OBJDIR)/mlp_bf16.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)

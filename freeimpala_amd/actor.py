@@ -115,6 +115,12 @@ class Actor:
         a = np.frombuffer(p, np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p)
         check(lib().fi_actor_set_params(self._h, a.ctypes.data, a.nbytes, version), "fi_actor_set_params")
 
+    def set_mlp_precision(self, precision) -> None:
+        """include/fi_mlp.h: "fp32" | "bf16" on an MLP actor, before its first act call. In bf16 mode the forward is the
+        learner's kernel: the logits of a row are the learner's for the same observation, bit for bit."""
+        from . import mlp_bf16
+        check(mlp_bf16.lib().fi_actor_set_mlp_precision(self._h, mlp_bf16.precision(precision)), "fi_actor_set_mlp_precision")
+
     # --- parameters from device memory, in stream order (include/fi_publish.h)
     def set_params_dev(self, learner) -> None:
         """The learner's newest publication (``learner.publish()``), enqueued on this handle's stream:

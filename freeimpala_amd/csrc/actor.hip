@@ -27,6 +27,7 @@
 
 #include "atari.h"
 #include "fi_actor.h"
+#include "fi_mlp.h"
 #include "fi_common.h"
 #include "fi_env.h"
 #include "fi_publish.h"
@@ -222,7 +223,11 @@ struct fi_actor {
     uint8_t* stacks = nullptr;   // Atari: the environments' stacks, pushed by act_planes
     uint8_t* planes = nullptr;   // Atari: (N, 7056) then the N start flags
     AtariNet* atari = nullptr;
-    float* h1 = nullptr;  // MLP
+    float* h1 = nullptr;  // MLP; bf16 in the same buffers under FI_MLP_BF16 (fi_mlp.h), the slab's images in img
+    int mlp_prec = FI_MLP_FP32;
+    __bf16* img = nullptr;
+    const MlpBf16Ops* bf = nullptr;  // mlp_bf16.hip's launchers, handed in with the mode
+    bool acted = false;  // an act call has run its forward
     float* h2 = nullptr;
     // outputs, one device block and one D2H copy: actions | values | logits | non-finite row count
     char* out = nullptr;
@@ -395,6 +400,31 @@ extern "C" void fi_actor_destroy(fi_actor* a) {
 extern "C" size_t fi_actor_param_count(const fi_actor* a) { return a ? a->nparams : 0; }
 extern "C" uint64_t fi_actor_version(const fi_actor* a) { return a ? a->version : 0; }
 
+// fi_mlp.h: the images of the actor's slab, behind every hand-over of parameters (nothing on an fp32 handle)
+static int mlp_sync_weights(fi_actor* a) {
+    if (a->mlp_prec != FI_MLP_BF16) return FI_OK;
+    return a->bf->weights(a->params, a->D, a->H, a->A, a->img, a->stream);
+}
+
+int fi::actor_set_mlp_precision(fi_actor* a, int prec, const MlpBf16Ops* ops) {
+    FI_REQUIRE(a, "actor_set_mlp_precision: null actor");
+    FI_REQUIRE(a->cfg.arch == FI_ARCH_MLP, "actor_set_mlp_precision: only the MLP policy has precision modes");
+    FI_REQUIRE(prec == FI_MLP_FP32 || prec == FI_MLP_BF16, "actor_set_mlp_precision: unknown precision");
+    if (a->acted) return fail(FI_ERR_STATE, "actor_set_mlp_precision: the handle has acted (choose the precision before the first act call)");
+    if (prec == FI_MLP_BF16 && !ops->supported(a->D, a->H, a->A))
+        return fail(FI_ERR_UNSUPPORTED, "actor_set_mlp_precision: bf16 takes 1 <= obs_dim <= 128, hidden a multiple of 32 in "
+                                        "32..256 and 2 <= num_actions <= 64; this handle has obs_dim " + std::to_string(a->D) +
+                                        ", hidden " + std::to_string(a->H) + ", num_actions " + std::to_string(a->A) +
+                                        " and stays in fp32");
+    FI_HIP_CHECK(hipSetDevice(a->dev));
+    if (prec == FI_MLP_BF16 && !a->img)
+        FI_TRY(dalloc(a, (void**)&a->img, ops->image_elems(a->D, a->H, a->A) * sizeof(__bf16)));
+    a->mlp_prec = prec;
+    a->bf = ops;
+    if (a->have_params) FI_TRY(mlp_sync_weights(a));
+    return FI_OK;
+}
+
 static int set_params(fi_actor* a, const void* src, size_t bytes, uint64_t version) {
     FI_REQUIRE(a && src, "actor_set_params: null argument");
     FI_HIP_CHECK(hipSetDevice(a->dev));
@@ -417,6 +447,7 @@ static int set_params(fi_actor* a, const void* src, size_t bytes, uint64_t versi
     }
     FI_HIP_CHECK(hipMemcpyAsync(a->params, p, a->nparams * 4, hipMemcpyHostToDevice, a->stream));
     if (a->atari) FI_TRY(atari_sync_weights(a->atari, a->params, a->stream));
+    FI_TRY(mlp_sync_weights(a));
     FI_HIP_CHECK(hipStreamSynchronize(a->stream));
     a->version = version;
     a->have_params = true;
@@ -441,6 +472,7 @@ extern "C" int fi_actor_set_params_ptr(fi_actor* a, const float* params_dev, siz
     FI_HIP_CHECK(hipMemcpyAsync(a->params, params_dev, count * sizeof(float), hipMemcpyDeviceToDevice, a->stream));
     FI_HIP_CHECK(hipEventRecord(a->params_read, a->stream));  // behind the copy: the source is free again
     if (a->atari) FI_TRY(atari_sync_weights(a->atari, a->params, a->stream));
+    FI_TRY(mlp_sync_weights(a));
     a->version = version;
     a->have_params = true;
     if (read_event_out) *read_event_out = (void*)a->params_read;
@@ -481,6 +513,10 @@ static int mlp_forward(fi_actor* a, const float* obs, float* logits, float* valu
     const float* b2 = W2 + (size_t)H * H;
     const float* Wh = b2 + H;
     const float* bh = Wh + (size_t)H * (A + 1);
+    a->acted = true;
+    if (a->mlp_prec == FI_MLP_BF16)  // the learner's kernel: a row's logits are the learner's, bit for bit
+        return a->bf->fwd(obs, a->N, D, H, A, a->img, a->params, (__bf16*)a->h1, (__bf16*)a->h2, logits, values,
+                                  a->stream);
     FI_TRY(f32_linear_fwd(obs, a->N, D, W1, b1, H, true, a->h1, a->stream));
     FI_TRY(f32_linear_fwd(a->h1, a->N, H, W2, b2, H, true, a->h2, a->stream));
     FI_TRY(f32_heads_fwd(a->h2, a->N, H, Wh, bh, A, logits, values, a->stream));

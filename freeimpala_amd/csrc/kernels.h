@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "fi_actor.h"
 #include "fi_diag.h"
 #include "fi_gather.h"
 #include "fi_kl.h"
@@ -59,6 +60,38 @@ bool f32_heads_bwd_fused_supported(int H, int A);
 constexpr int kHeadsFusedGrid = 512;
 int f32_heads_bwd_fused(const HeadsGrad& g, const float* h2, const float* Wh, int H, float* dz2, float* slab,
                         float* cs_slab, int grid, hipStream_t s);
+
+// mlp_bf16.hip (MLP, bf16 mode: include/fi_mlp.h). img: the five weight images of one parameter slab
+// (W1, W2, Wh in B-operand order for the forward, W2^T and Wh^T for the data gradients), 16-byte aligned
+bool mlp_bf16_supported(int D, int H, int A);
+size_t mlp_bf16_image_elems(int D, int H, int A);
+int mlp_weights_bf16(const float* params, int D, int H, int A, __bf16* img, hipStream_t s);
+// one launch: h1, h2 (M, H) bf16, logits (M, A) and values (M) fp32; params for the fp32 biases
+int mlp_fwd_fused_bf16(const float* obs, int M, int D, int H, int A, const __bf16* img, const float* params, __bf16* h1,
+                       __bf16* h2, float* logits, float* values, hipStream_t s);
+// dz2 (rows, H) bf16, and the heads' gradient slabs: slab splits x (H x (A + 1)), cs splits x (A + 1)
+int mlp_heads_bwd_bf16(const HeadsGrad& g, const __bf16* h2, const __bf16* img, int D, int H, __bf16* dz2, int splits,
+                       float* slab, float* cs, hipStream_t s);
+int mlp_dgrad_bf16(const __bf16* dz2, int M, int D, int H, int A, const __bf16* img, const __bf16* h1, __bf16* dz1,
+                   hipStream_t s);
+// X^T dY over `splits` row slices: X (M, I) fp32 (x_f32) or bf16, dY (M, N) bf16; slab splits x (I x N), cs splits x N
+int mlp_wgrad_bf16(const void* X, bool x_f32, int M, int I, const __bf16* dY, int N, int splits, float* slab, float* cs,
+                   hipStream_t s);
+// The launchers above as pointers: mlp_bf16.hip, which holds fi_mlp.h's C entry points, hands them to the
+// handle with the mode, so learner.cpp and actor.hip name nothing of mlp_bf16.hip and link without it
+struct MlpBf16Ops {
+    decltype(&mlp_bf16_supported) supported;
+    decltype(&mlp_bf16_image_elems) image_elems;
+    decltype(&mlp_weights_bf16) weights;
+    decltype(&mlp_fwd_fused_bf16) fwd;
+    decltype(&mlp_heads_bwd_bf16) heads_bwd;
+    decltype(&mlp_dgrad_bf16) dgrad;
+    decltype(&mlp_wgrad_bf16) wgrad;
+};
+// learner.cpp / actor.hip: fi_mlp.h's setters behind their argument checks
+int learner_set_mlp_precision(fi_learner* l, int prec, const MlpBf16Ops* ops);
+int learner_mlp_precision(const fi_learner* l);
+int actor_set_mlp_precision(::fi_actor* a, int prec, const MlpBf16Ops* ops);
 
 // weights.hip: dlog (T, B, A) and the first T rows of dval times w[b] in place (include/fi_weights.h).
 // learner.cpp takes it as a pointer, as it takes the ingests below

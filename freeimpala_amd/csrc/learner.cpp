@@ -26,6 +26,7 @@
 
 #include "atari.h"
 #include "fi_common.h"
+#include "fi_mlp.h"
 #include "fi_rollout.h"
 #include "fi_train.h"
 #include "host_util.h"
@@ -64,10 +65,15 @@ struct fi_learner {
     float* rew = nullptr;
     float* disc = nullptr;
     // network / loss tensors
-    float* h1 = nullptr;  // MLP
-    float* h2 = nullptr;
-    float* dz1 = nullptr;
-    float* dz2 = nullptr;
+    // MLP: fp32 (rows, H), or bf16 of the same shape under FI_MLP_BF16 (fi_mlp.h), then with the five
+    // weight images of the slab behind them in img
+    void* h1 = nullptr;
+    void* h2 = nullptr;
+    void* dz1 = nullptr;
+    void* dz2 = nullptr;
+    int mlp_prec = FI_MLP_FP32;
+    __bf16* img = nullptr;
+    const MlpBf16Ops* bf = nullptr;  // mlp_bf16.hip's launchers, handed in with the mode
     float* logits = nullptr;
     float* values = nullptr;
     float* vs = nullptr;
@@ -322,10 +328,7 @@ static int create(const fi_learner_config* cfg, fi_learner** out) {
         l->nparams = (size_t)D * H + H + (size_t)H * H + H + (size_t)H * O + O;
         init_mlp_params(l, init);
         FI_TRY(dalloc_n(l, &l->obs, rows * D));
-        FI_TRY(dalloc_n(l, &l->h1, rows * H));
-        FI_TRY(dalloc_n(l, &l->h2, rows * H));
-        FI_TRY(dalloc_n(l, &l->dz1, rows * H));
-        FI_TRY(dalloc_n(l, &l->dz2, rows * H));
+        for (void** a : {&l->h1, &l->h2, &l->dz1, &l->dz2}) FI_TRY(dalloc(l, a, rows * H * sizeof(float)));
         // weight-gradient R-slices: 384 at R = 413,696 gives the K = 128 layer 1,536 workgroups
         // (6 per CU, the kernel's occupancy) -- with 128 its 512 workgroups left the CUs
         // latency-bound (wgrad_l1 0.44 -> 0.29 ms, wgrad_l2 0.60 -> 0.54 ms; 512 slices measured
@@ -414,6 +417,47 @@ extern "C" int fi_learner_set_record_format(fi_learner* l, int fmt) {
         return fail(FI_ERR_STATE, "set_record_format: the staging buffers exist (choose the format before the "
                                   "first host batch)");
     l->rec_format = fmt;
+    return FI_OK;
+}
+// fi_mlp.h: the images of the parameter slab, behind every write of it (nothing on an fp32 handle)
+static int mlp_sync_weights(fi_learner* l) {
+    if (l->mlp_prec != FI_MLP_BF16) return FI_OK;
+    return l->bf->weights(l->params, l->D, l->H, l->A, l->img, l->stream);
+}
+int fi::learner_mlp_precision(const fi_learner* l) { return l ? l->mlp_prec : FI_ERR_INVALID; }
+int fi::learner_set_mlp_precision(fi_learner* l, int prec, const MlpBf16Ops* ops) {
+    FI_REQUIRE(l, "set_mlp_precision: null learner");
+    FI_REQUIRE(l->cfg.arch == FI_ARCH_MLP, "set_mlp_precision: only the MLP policy has precision modes");
+    FI_REQUIRE(prec == FI_MLP_FP32 || prec == FI_MLP_BF16, "set_mlp_precision: unknown precision");
+    if (l->stepped || l->step_count != 0 || l->in_flight)
+        return fail(FI_ERR_STATE, "set_mlp_precision: the handle has stepped (choose the precision before the first step)");
+    if (prec == l->mlp_prec) return FI_OK;
+    if (prec == FI_MLP_BF16 && !ops->supported(l->D, l->H, l->A))
+        return fail(FI_ERR_UNSUPPORTED, "set_mlp_precision: bf16 takes 1 <= obs_dim <= 128, hidden a multiple of 32 in 32..256 "
+                                        "and 2 <= num_actions <= 64; this handle has obs_dim " + std::to_string(l->D) +
+                                        ", hidden " + std::to_string(l->H) + ", num_actions " + std::to_string(l->A) +
+                                        " and stays in fp32");
+    FI_HIP_CHECK(hipSetDevice(l->dev));
+    FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+    // the activations and data gradients change their element size; the images exist in bf16 mode only
+    const size_t elem = prec == FI_MLP_BF16 ? sizeof(__bf16) : sizeof(float);
+    auto drop = [l](void* p) {
+        if (!p) return;
+        l->allocs.erase(std::remove(l->allocs.begin(), l->allocs.end(), p), l->allocs.end());
+        (void)hipFree(p);
+    };
+    for (void** a : {&l->h1, &l->h2, &l->dz1, &l->dz2, (void**)&l->img}) {
+        drop(*a);
+        *a = nullptr;
+    }
+    for (void** a : {&l->h1, &l->h2, &l->dz1, &l->dz2}) FI_TRY(dalloc(l, a, (size_t)l->rows * l->H * elem));
+    l->mlp_prec = prec;
+    l->bf = ops;
+    if (prec == FI_MLP_BF16) {
+        FI_TRY(dalloc_n(l, &l->img, ops->image_elems(l->D, l->H, l->A)));
+        FI_TRY(mlp_sync_weights(l));
+        FI_HIP_CHECK(hipStreamSynchronize(l->stream));
+    }
     return FI_OK;
 }
 extern "C" void* fi_learner_stream(fi_learner* l) { return l ? (void*)l->stream : nullptr; }
@@ -535,15 +579,21 @@ struct BucketAllReduce : GradReadyHook {
 static int mlp_forward(fi_learner* l, const float* params, float* logits, float* values) {
     const int D = l->D, H = l->H, A = l->A;
     const bool own = params == l->params;
+    if (l->mlp_prec == FI_MLP_BF16) {  // l->img holds the images of `params` (target_forward swaps them)
+        Tag t(l, own ? "mlp_fwd_fused" : nullptr);
+        return l->bf->fwd(l->obs, l->rows, D, H, A, l->img, params, (__bf16*)l->h1, (__bf16*)l->h2, logits, values,
+                                  l->stream);
+    }
     const float* W1 = params;
     const float* b1 = W1 + (size_t)D * H;
     const float* W2 = b1 + H;
     const float* b2 = W2 + (size_t)H * H;
     const float* Wh = b2 + H;
     const float* bh = Wh + (size_t)H * (A + 1);
-    { Tag t(l, own ? "mlp_fwd_l1" : nullptr); FI_TRY(f32_linear_fwd(l->obs, l->rows, D, W1, b1, H, true, l->h1, l->stream)); }
-    { Tag t(l, own ? "mlp_fwd_l2" : nullptr); FI_TRY(f32_linear_fwd(l->h1, l->rows, H, W2, b2, H, true, l->h2, l->stream)); }
-    { Tag t(l, own ? "mlp_fwd_heads" : nullptr); FI_TRY(f32_heads_fwd(l->h2, l->rows, H, Wh, bh, A, logits, values, l->stream)); }
+    float *h1 = (float*)l->h1, *h2 = (float*)l->h2;
+    { Tag t(l, own ? "mlp_fwd_l1" : nullptr); FI_TRY(f32_linear_fwd(l->obs, l->rows, D, W1, b1, H, true, h1, l->stream)); }
+    { Tag t(l, own ? "mlp_fwd_l2" : nullptr); FI_TRY(f32_linear_fwd(h1, l->rows, H, W2, b2, H, true, h2, l->stream)); }
+    { Tag t(l, own ? "mlp_fwd_heads" : nullptr); FI_TRY(f32_heads_fwd(h2, l->rows, H, Wh, bh, A, logits, values, l->stream)); }
     return FI_OK;
 }
 
@@ -553,6 +603,17 @@ static int wgrad(fi_learner* l, const char* tag, const float* X, int I, const fl
     { Tag t(l, tag); FI_TRY(f32_linear_wgrad_partial(X, l->rows, I, dY, N, l->splits, l->slab, cs, l->stream)); }
     { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(l->slab, l->splits, (size_t)I * N, gW, l->stream)); }
     { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(cs, l->splits, (size_t)N, gb, l->stream)); }
+    return FI_OK;
+}
+
+// one weight gradient of the bf16 mode: slabs over the row slices, then the fixed-order sums
+static int wgrad_bf16(fi_learner* l, const char* tag, const void* X, bool x_f32, int I, const __bf16* dY, float* gW,
+                      float* gb) {
+    const int H = l->H;
+    float* cs = l->slab + l->slab_floats - (size_t)l->splits * 4096;
+    { Tag t(l, tag); FI_TRY(l->bf->wgrad(X, x_f32, l->rows, I, dY, H, l->splits, l->slab, cs, l->stream)); }
+    { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(l->slab, l->splits, (size_t)I * H, gW, l->stream)); }
+    { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(cs, l->splits, (size_t)H, gb, l->stream)); }
     return FI_OK;
 }
 
@@ -568,24 +629,38 @@ static int mlp_backward(fi_learner* l, GradReadyHook* gr) {
     float* gbh = gWh + (size_t)H * O;
     HeadsGrad g{l->dlogits, l->dvalue, l->rows, l->TB, A};
     float* cs = l->slab + l->slab_floats - (size_t)l->splits * 4096;
+    if (l->mlp_prec == FI_MLP_BF16) {  // fi_mlp.h: the same buckets at the same places as below
+        __bf16 *h1 = (__bf16*)l->h1, *h2 = (__bf16*)l->h2, *dz1 = (__bf16*)l->dz1, *dz2 = (__bf16*)l->dz2;
+        { Tag t(l, "mlp_heads_bwd"); FI_TRY(l->bf->heads_bwd(g, h2, l->img, D, H, dz2, l->splits, l->slab, cs, l->stream)); }
+        { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(l->slab, l->splits, (size_t)H * O, gWh, l->stream)); }
+        { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(cs, l->splits, (size_t)O, gbh, l->stream)); }
+        FI_TRY(gr->ready((size_t)(gWh - l->grads), (size_t)H * O + O));
+        FI_TRY(wgrad_bf16(l, "mlp_wgrad_l2", h1, false, H, dz2, gW2, gb2));
+        FI_TRY(gr->ready((size_t)(gW2 - l->grads), (size_t)H * H + H));
+        { Tag t(l, "mlp_dgrad_l2"); FI_TRY(l->bf->dgrad(dz2, l->rows, D, H, A, l->img, h1, dz1, l->stream)); }
+        FI_TRY(wgrad_bf16(l, "mlp_wgrad_l1", l->obs, true, D, dz1, gW1, gb1));
+        FI_TRY(gr->ready(0, (size_t)D * H + H));
+        return FI_OK;
+    }
+    float *h1 = (float*)l->h1, *h2 = (float*)l->h2, *dz1 = (float*)l->dz1, *dz2 = (float*)l->dz2;
     if (f32_heads_bwd_fused_supported(H, A) && (size_t)kHeadsFusedGrid * (H * O + O) <= l->slab_floats) {
         // both heads gradients in one pass over h2 (weight-gradient slabs, then dz2)
         float* hcs = l->slab + (size_t)kHeadsFusedGrid * H * O;
-        { Tag t(l, "mlp_heads_bwd"); FI_TRY(f32_heads_bwd_fused(g, l->h2, Wh, H, l->dz2, l->slab, hcs, kHeadsFusedGrid, l->stream)); }
+        { Tag t(l, "mlp_heads_bwd"); FI_TRY(f32_heads_bwd_fused(g, h2, Wh, H, dz2, l->slab, hcs, kHeadsFusedGrid, l->stream)); }
         { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(l->slab, kHeadsFusedGrid, (size_t)H * O, gWh, l->stream)); }
         { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(hcs, kHeadsFusedGrid, (size_t)O, gbh, l->stream)); }
         FI_TRY(gr->ready((size_t)(gWh - l->grads), (size_t)H * O + O));
     } else {
-        { Tag t(l, "mlp_wgrad_heads"); FI_TRY(f32_heads_wgrad_partial(l->h2, H, g, l->splits, l->slab, cs, l->stream)); }
+        { Tag t(l, "mlp_wgrad_heads"); FI_TRY(f32_heads_wgrad_partial(h2, H, g, l->splits, l->slab, cs, l->stream)); }
         { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(l->slab, l->splits, (size_t)H * O, gWh, l->stream)); }
         { Tag t(l, "reduce_slabs"); FI_TRY(reduce_slabs(cs, l->splits, (size_t)O, gbh, l->stream)); }
         FI_TRY(gr->ready((size_t)(gWh - l->grads), (size_t)H * O + O));
-        { Tag t(l, "mlp_dgrad_heads"); FI_TRY(f32_heads_dgrad(g, Wh, H, l->h2, l->dz2, l->stream)); }
+        { Tag t(l, "mlp_dgrad_heads"); FI_TRY(f32_heads_dgrad(g, Wh, H, h2, dz2, l->stream)); }
     }
-    FI_TRY(wgrad(l, "mlp_wgrad_l2", l->h1, H, l->dz2, H, gW2, gb2));
+    FI_TRY(wgrad(l, "mlp_wgrad_l2", h1, H, dz2, H, gW2, gb2));
     FI_TRY(gr->ready((size_t)(gW2 - l->grads), (size_t)H * H + H));
-    { Tag t(l, "mlp_dgrad_l2"); FI_TRY(f32_linear_dgrad(l->dz2, l->rows, H, W2, H, l->h1, l->dz1, l->stream)); }
-    FI_TRY(wgrad(l, "mlp_wgrad_l1", l->obs, D, l->dz1, H, gW1, gb1));
+    { Tag t(l, "mlp_dgrad_l2"); FI_TRY(f32_linear_dgrad(dz2, l->rows, H, W2, H, h1, dz1, l->stream)); }
+    FI_TRY(wgrad(l, "mlp_wgrad_l1", l->obs, D, dz1, H, gW1, gb1));
     FI_TRY(gr->ready(0, (size_t)D * H + H));
     return FI_OK;
 }
@@ -674,19 +749,23 @@ static BatchTensors batch_tensors(const fi_learner* l) {
 // the target parameters, in front of the learner's forward, which overwrites the activations again
 static int target_forward(fi_learner* l) {
     const TargetBlock* tb = l->target;
-    if (l->cfg.arch == FI_ARCH_MLP) {
+    if (l->cfg.arch == FI_ARCH_MLP && l->mlp_prec == FI_MLP_FP32) {
         Tag t(l, "target_forward");
         return mlp_forward(l, tb->theta, tb->tlogits, tb->tvalues);
     }
+    auto sync_weights = [l](const float* p) {
+        return l->atari ? atari_sync_weights(l->atari, p, l->stream) : l->bf->weights(p, l->D, l->H, l->A, l->img, l->stream);
+    };
     // the net points at theta- between the two syncs only: the way back is taken whatever the forward returned
     int rc;
-    { Tag t(l, "target_weights_bf16"); rc = atari_sync_weights(l->atari, tb->theta, l->stream); }
+    { Tag t(l, "target_weights_bf16"); rc = sync_weights(tb->theta); }
     if (rc == FI_OK) {
         Tag t(l, "target_forward");
-        rc = atari_forward(l->atari, l->frames, tb->tlogits, tb->tvalues, l->stream, nullptr);
+        rc = l->atari ? atari_forward(l->atari, l->frames, tb->tlogits, tb->tvalues, l->stream, nullptr)
+                      : mlp_forward(l, tb->theta, tb->tlogits, tb->tvalues);
     }
     int back;
-    { Tag t(l, "target_weights_back"); back = atari_sync_weights(l->atari, l->params, l->stream); }
+    { Tag t(l, "target_weights_back"); back = sync_weights(l->params); }
     return rc != FI_OK ? rc : back;
 }
 
@@ -847,6 +926,9 @@ static int run_step(fi_learner* l, const BatchSource* src, fi_step_stats* out) {
     if (l->atari) {
         Tag t(l, "weights_bf16");
         FI_TRY(atari_sync_weights(l->atari, l->params, l->stream));
+    } else if (l->mlp_prec == FI_MLP_BF16) {
+        Tag t(l, "weights_bf16");
+        FI_TRY(mlp_sync_weights(l));
     }
     mark(l, FI_PHASE_COUNT);
     if (out) FI_HIP_CHECK(hipEventRecord(l->ev_b, l->stream));
@@ -1529,6 +1611,7 @@ extern "C" int fi_learner_set_params(fi_learner* l, const void* src, size_t byte
     }
     FI_HIP_CHECK(hipMemcpyAsync(l->params, p, l->nparams * 4, hipMemcpyHostToDevice, l->stream));
     if (l->atari) FI_TRY(atari_sync_weights(l->atari, l->params, l->stream));
+    FI_TRY(mlp_sync_weights(l));
     FI_HIP_CHECK(hipMemsetAsync(l->bad + 2, 0, 2 * sizeof(int), l->stream));  // a new version line
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
     l->version = version;
@@ -1580,6 +1663,7 @@ extern "C" int fi_learner_load_state(fi_learner* l, const void* src, size_t byte
     FI_HIP_CHECK(hipMemcpyAsync(l->opt_m, f + l->nparams, l->nparams * 4, hipMemcpyHostToDevice, l->stream));
     FI_HIP_CHECK(hipMemcpyAsync(l->opt_v, f + 2 * l->nparams, l->nparams * 4, hipMemcpyHostToDevice, l->stream));
     if (l->atari) FI_TRY(atari_sync_weights(l->atari, l->params, l->stream));
+    FI_TRY(mlp_sync_weights(l));
     FI_HIP_CHECK(hipMemsetAsync(l->bad + 2, 0, 2 * sizeof(int), l->stream));
     FI_HIP_CHECK(hipStreamSynchronize(l->stream));
     l->step_count = h.step_count;
@@ -1702,6 +1786,7 @@ extern "C" int fi_learner_read_tensor(fi_learner* l, const char* name, void* dst
 extern "C" int fi_learner_tensor(fi_learner* l, const char* name, void** ptr, size_t* bytes) {
     FI_REQUIRE(l && name && ptr && bytes, "tensor: null argument");
     const size_t rows = l->rows, TB = l->TB, A = l->A;
+    const size_t act = l->mlp_prec == FI_MLP_BF16 ? 2 : 4;  // fi_mlp.h: bf16 activations and data gradients
     struct E {
         const char* n;
         void* p;
@@ -1717,8 +1802,10 @@ extern "C" int fi_learner_tensor(fi_learner* l, const char* name, void** ptr, si
         {"logits", l->logits, rows * A * 4},     {"values", l->values, rows * 4},
         {"vs", l->vs, TB * 4},                   {"pg_adv", l->pg_adv, TB * 4},
         {"dlogits", l->dlogits, TB * A * 4},     {"dvalue", l->dvalue, rows * 4},
-        {"losses", l->small, 3 * 8},             {"h1", l->h1, l->h1 ? rows * l->H * 4 : 0},
-        {"h2", l->h2, l->h2 ? rows * l->H * 4 : 0},
+        {"losses", l->small, 3 * 8},             {"h1", l->h1, l->h1 ? rows * l->H * act : 0},
+        {"h2", l->h2, l->h2 ? rows * l->H * act : 0},
+        {"dz1", l->dz1, l->dz1 ? rows * l->H * act : 0},
+        {"dz2", l->dz2, l->dz2 ? rows * l->H * act : 0},
     };
     for (auto& e : t)
         if (std::strcmp(e.n, name) == 0) {

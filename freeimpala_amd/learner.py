@@ -88,6 +88,20 @@ class DeviceLearner:
         first host batch."""
         check(lib().fi_learner_set_record_format(self._h, fmt), "fi_learner_set_record_format")
 
+    # --- the MLP policy's numeric mode (include/fi_mlp.h; the rule: freeimpala_amd/mlp_bf16.py)
+    def set_mlp_precision(self, precision) -> None:
+        """"fp32" (the default: exact fp32 MFMA) or "bf16" (bf16 operands and stored activations, fp32
+        accumulation), before the first step. bf16 takes obs_dim <= 128, hidden a multiple of 32 in 32..256; another
+        width is refused and the handle stays in fp32."""
+        from . import mlp_bf16
+        check(mlp_bf16.lib().fi_learner_set_mlp_precision(self._h, mlp_bf16.precision(precision)),
+              "fi_learner_set_mlp_precision")
+
+    @property
+    def mlp_precision(self) -> str:
+        from . import mlp_bf16
+        return "bf16" if mlp_bf16.lib().fi_learner_mlp_precision(self._h) == mlp_bf16.BF16 else "fp32"
+
     # --- the step
     def step(self, batch: Sequence[bytes | bytearray | np.ndarray] | HostBatch,
              stats: bool = True) -> dict:

@@ -18,6 +18,7 @@
 #include "fi_env.h"
 #include "fi_explore.h"
 #include "fi_gather.h"
+#include "fi_mlp.h"
 #include "fi_publish.h"
 #include "fi_rollout.h"
 
@@ -86,6 +87,8 @@ public:
         return ok(fi_actor_read_params(h_, out.data(), out.size()));
     }
     bool set_greedy(bool greedy) { return ok(fi_actor_set_mode(h_, greedy ? FI_ACT_GREEDY : FI_ACT_SAMPLE)); }
+    // include/fi_mlp.h: FI_MLP_FP32 or FI_MLP_BF16 on an MLP actor, before its first act call
+    bool set_mlp_precision(int precision) { return ok(fi_actor_set_mlp_precision(h_, precision)); }
     bool seed(uint64_t seed, uint64_t draw = 0) { return ok(fi_actor_seed(h_, seed, draw)); }
 
     // Exploration (include/fi_explore.h): the draw gets a temperature and one epsilon per environment

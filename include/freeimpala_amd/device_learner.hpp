@@ -42,6 +42,7 @@
 #include "fi_surrogate.h"
 #include "fi_vmpo.h"
 #include "fi_target.h"
+#include "fi_mlp.h"
 #include "fi_upgo.h"
 #include "fi_train.h"
 
@@ -643,6 +644,15 @@ public:
         if (enabled) *enabled = on != 0;
         return true;
     }
+    // The MLP policy's numeric mode on player p (include/fi_mlp.h): FI_MLP_FP32 or FI_MLP_BF16, before the player's
+    // first step. A width the bf16 mode does not take is refused and the player stays in fp32.
+    bool set_mlp_precision(size_t p, int precision) {
+        if (p >= handles_.size()) return fail(0, "player_index out of range");
+        for (fi_learner* h : shards_[p])
+            if (fi_learner_set_mlp_precision(h, precision) != FI_OK) return fail(p, fi_last_error());
+        return true;
+    }
+    int mlp_precision(size_t p) const { return p < handles_.size() ? fi_learner_mlp_precision(handles_[p]) : FI_ERR_INVALID; }
     // --starting-model resume (Model::loadFromDisk bytes + version).
     bool load(size_t p, const std::vector<char>& blob, uint64_t version) {
         if (p >= handles_.size()) return fail(0, "player_index out of range");

@@ -227,7 +227,12 @@ def main() -> None:
     ap.add_argument("--objective", choices=("vtrace", "surrogate"), default="vtrace")
     ap.add_argument("--clip", type=float, default=0.2, metavar="EPS")
     ap.add_argument("--normalize-adv", action="store_true")
+    # include/fi_mlp.h: the MLP policy's numeric mode. Catch is played from frames by the Atari policy, which has
+    # one mode (bf16 images already), so there is no MLP learner here for the option to reach
+    ap.add_argument("--mlp-precision", choices=("fp32", "bf16"), default="fp32")
     args = ap.parse_args()
+    if args.mlp_precision != "fp32":
+        print("train_catch: --mlp-precision applies to an MLP policy; this script trains the Atari policy only (ignored)")
     if args.diagnostics < 0:
         raise SystemExit("train_catch: --diagnostics K enqueues every K-th unroll, K >= 1 (0: off)")
     if args.overlap and args.publish != "device":
