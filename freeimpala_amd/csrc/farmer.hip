@@ -23,12 +23,16 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "farmer_lstm_bf16.h"
 #include "fi_common.h"
 #include "fi_farmer.h"
+#include "fi_farmer_lstm.h"
 #include "kernels.h"
 
 namespace fi {
@@ -798,6 +802,12 @@ struct fi_farmer {
     bool profiling = false;
     double prof_fwd = 0.0, prof_bwd = 0.0;
     int prof_steps = 0;
+    // the LSTM's bf16 mode (fi_farmer_lstm.h): gates, hprev and dG above are null while it is on
+    bool lstm_bf16 = false, used = false;  // used: a step or a forward has been enqueued
+    const LstmBf16Ops* ops = nullptr;      // farmer_lstm_bf16.hip's launchers, handed in with the mode
+    __bf16 *img = nullptr, *gates16 = nullptr, *hprev16 = nullptr, *dG16 = nullptr;
+    float* slab16 = nullptr;
+    int splits16 = 0;
     std::vector<void*> allocs;
 };
 
@@ -808,6 +818,20 @@ static int falloc(fi_farmer* f, float** p, size_t n) {
     f->allocs.push_back(q);
     *p = (float*)q;
     return FI_OK;
+}
+
+template <class P>
+static void ffree(fi_farmer* f, P** p) {
+    if (!*p) return;
+    f->allocs.erase(std::remove(f->allocs.begin(), f->allocs.end(), (void*)*p), f->allocs.end());
+    hipFree(*p);
+    *p = nullptr;
+}
+
+// the bf16 images follow every write of the parameters
+static int lstm_images(fi_farmer* f) {
+    if (!f->lstm_bf16) return FI_OK;
+    return f->ops->weights(f->params + f->off.wih, f->params + f->off.whh, f->img, f->stream);
 }
 
 static int splits_for(int M) { return std::max(1, std::min(16, M / 256)); }
@@ -842,11 +866,13 @@ static int forward(fi_farmer* f) {
     const Off& o = f->off;
     float* P = f->params;
     hipLaunchKernelGGL(lstm_prep_kernel, dim3((G + 255) / 256), dim3(256), 0, s, P + o.bih, P + o.bhh, f->bsum);
-    FI_TRY(f32_gemm_nt(f->z, IN, B * T, IN, P + o.wih, f->bsum, G, false, f->xp, s));
+    if (f->lstm_bf16) FI_TRY(f->ops->xproj(f->z, B * T, f->img, f->bsum, f->xp, s));
+    else FI_TRY(f32_gemm_nt(f->z, IN, B * T, IN, P + o.wih, f->bsum, G, false, f->xp, s));
     const int R = lstm_rows(B);
     const dim3 grid((B + R - 1) / R), blk(512);
     if (f->profiling) FI_HIP_CHECK(hipEventRecord(f->pe[0], s));
-    if (R == 1) hipLaunchKernelGGL(lstm_fwd_reg_kernel<1>, grid, blk, 0, s, f->xp, P + o.whh, B, T, f->gates, f->cst, f->hprev, f->cat);
+    if (f->lstm_bf16) FI_TRY(f->ops->fwd(f->xp, f->img, B, T, f->gates16, f->cst, f->hprev16, f->cat, s));
+    else if (R == 1) hipLaunchKernelGGL(lstm_fwd_reg_kernel<1>, grid, blk, 0, s, f->xp, P + o.whh, B, T, f->gates, f->cst, f->hprev, f->cat);
     else if (R == 2) hipLaunchKernelGGL(lstm_fwd_reg_kernel<2>, grid, blk, 0, s, f->xp, P + o.whh, B, T, f->gates, f->cst, f->hprev, f->cat);
     else hipLaunchKernelGGL(lstm_fwd_reg_kernel<4>, grid, blk, 0, s, f->xp, P + o.whh, B, T, f->gates, f->cst, f->hprev, f->cat);
     if (f->profiling) FI_HIP_CHECK(hipEventRecord(f->pe[1], s));
@@ -907,13 +933,18 @@ static int backward(fi_farmer* f) {
         const int R = lstm_rows(B);
         const dim3 grid((B + R - 1) / R), blk(512);
         if (f->profiling) FI_HIP_CHECK(hipEventRecord(f->pe[2], s));
-        if (R == 1) hipLaunchKernelGGL(lstm_bwd_reg_kernel<1>, grid, blk, 0, s, f->gates, f->cst, P + o.whh, f->dcat, B, T, f->dG);
+        if (f->lstm_bf16) FI_TRY(f->ops->bwd(f->gates16, f->cst, f->img, f->dcat, B, T, f->dG16, s));
+        else if (R == 1) hipLaunchKernelGGL(lstm_bwd_reg_kernel<1>, grid, blk, 0, s, f->gates, f->cst, P + o.whh, f->dcat, B, T, f->dG);
         else if (R == 2) hipLaunchKernelGGL(lstm_bwd_reg_kernel<2>, grid, blk, 0, s, f->gates, f->cst, P + o.whh, f->dcat, B, T, f->dG);
         else hipLaunchKernelGGL(lstm_bwd_reg_kernel<4>, grid, blk, 0, s, f->gates, f->cst, P + o.whh, f->dcat, B, T, f->dG);
         if (f->profiling) FI_HIP_CHECK(hipEventRecord(f->pe[3], s));
     }
-    FI_TRY(wgrad(f, f->dG, B * T, G, f->z, IN, IN, Gd + o.wih, Gd + o.bih));
-    FI_TRY(wgrad(f, f->dG, B * T, G, f->hprev, H, H, Gd + o.whh, nullptr));
+    if (f->lstm_bf16) {
+        FI_TRY(f->ops->wgrads(f->dG16, f->z, f->hprev16, B * T, f->splits16, f->slab16, Gd + o.wih, Gd + o.whh, Gd + o.bih, s));
+    } else {
+        FI_TRY(wgrad(f, f->dG, B * T, G, f->z, IN, IN, Gd + o.wih, Gd + o.bih));
+        FI_TRY(wgrad(f, f->dG, B * T, G, f->hprev, H, H, Gd + o.whh, nullptr));
+    }
     hipLaunchKernelGGL(copy_kernel, dim3((G + 255) / 256), dim3(256), 0, s, Gd + o.bih, Gd + o.bhh, G);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
@@ -933,7 +964,7 @@ static int optimize(fi_farmer* f) {
                        f->v, n, c.lr, c.weight_decay, c.beta1, c.beta2, c.eps, neg_ss, bc2s, decay,
                        f->small ? f->sync + 1 : nullptr);
     FI_HIP_CHECK(hipGetLastError());
-    return FI_OK;
+    return lstm_images(f);
 }
 
 static int stage_inputs(fi_farmer* f, const float* z, const float* x, const float* y, int on_device) {
@@ -1084,6 +1115,7 @@ extern "C" int fi_farmer_set_params(fi_farmer* f, const float* host, size_t n) {
     FI_HIP_CHECK(hipMemcpyAsync(f->params, host, n * 4, hipMemcpyHostToDevice, f->stream));
     FI_HIP_CHECK(hipMemsetAsync(f->m, 0, n * 4, f->stream));
     FI_HIP_CHECK(hipMemsetAsync(f->v, 0, n * 4, f->stream));
+    FI_TRY(lstm_images(f));
     FI_HIP_CHECK(hipStreamSynchronize(f->stream));
     f->step = 0;
     return FI_OK;
@@ -1113,6 +1145,7 @@ extern "C" int fi_farmer_train_step(fi_farmer* f, const float* z, const float* x
     FI_REQUIRE(f && z && x && targets, "farmer_train_step: null argument");
     FI_HIP_CHECK(hipSetDevice(f->dev));
     FI_TRY(stage_inputs(f, z, x, targets, inputs_on_device));
+    f->used = true;
     if (out) FI_HIP_CHECK(hipEventRecord(f->e0, f->stream));
     FI_TRY(forward(f));
     FI_TRY(backward(f));
@@ -1147,6 +1180,7 @@ extern "C" int fi_farmer_forward(fi_farmer* f, const float* z, const float* x, i
     FI_REQUIRE(f && z && x && values, "farmer_forward: null argument");
     FI_HIP_CHECK(hipSetDevice(f->dev));
     FI_TRY(stage_inputs(f, z, x, nullptr, inputs_on_device));
+    f->used = true;
     FI_TRY(forward(f));
     FI_TRY(d2h(f, f->val, values, (size_t)f->B));
     return fused_status(f, "farmer_forward");
@@ -1155,6 +1189,8 @@ extern "C" int fi_farmer_forward(fi_farmer* f, const float* z, const float* x, i
 extern "C" int fi_farmer_tensor(fi_farmer* f, const char* name, void** ptr, size_t* bytes) {
     FI_REQUIRE(f && name && ptr && bytes, "farmer_tensor: null argument");
     const size_t B = f->B, BT = (size_t)f->B * f->T;
+    const bool bf = f->lstm_bf16;
+    const size_t es = bf ? 2 : 4;  // bytes of an element of gates, hprev and dG
     struct E {
         const char* n;
         void* p;
@@ -1162,17 +1198,68 @@ extern "C" int fi_farmer_tensor(fi_farmer* f, const char* name, void** ptr, size
     } t[] = {{"params", f->params, f->off.total * 4}, {"grads", f->grads, f->off.total * 4},
              {"values", f->val, B * 4},               {"z", f->z, BT * IN * 4},
              {"x", f->x, B * XD * 4},                 {"targets", f->y, B * 4},
-             {"gates", f->gates, BT * G * 4},         {"h_last", f->cat, B * CAT * 4},
+             {"h_last", f->cat, B * CAT * 4},         {"xp", f->xp, BT * G * 4},
+             {"cst", f->cst, BT * H * 4},             {"dcat", f->dcat, B * CAT * 4},
+             {"gates", bf ? (void*)f->gates16 : f->gates, BT * G * es},
+             {"hprev", bf ? (void*)f->hprev16 : f->hprev, BT * H * es},
+             {"dG", bf ? (void*)f->dG16 : f->dG, BT * G * es},
+             {"wih_bf16", f->img, kLstmImgWhh * 2},
+             {"whh_bf16", bf ? f->img + kLstmImgWhh : nullptr, (kLstmImgElems - kLstmImgWhh) * 2},
              {"act1", f->act[1], B * DW * 4},         {"act2", f->act[2], B * DW * 4},
              {"act3", f->act[3], B * DW * 4},         {"act4", f->act[4], B * DW * 4},
              {"act5", f->act[5], B * DW * 4}};
     for (const E& e : t)
-        if (std::strcmp(e.n, name) == 0) {
+        if (e.p && std::strcmp(e.n, name) == 0) {
             *ptr = e.p;
             *bytes = e.b;
             return FI_OK;
         }
     return fail(FI_ERR_INVALID, std::string("farmer_tensor: unknown tensor ") + name);
+}
+
+// fi_farmer_lstm.h (the C entry points are farmer_lstm_bf16.hip's, which hands its launchers in)
+int fi::farmer::set_lstm_precision(fi_farmer* f, int precision, const LstmBf16Ops* ops) {
+    FI_REQUIRE(f && ops, "farmer_set_lstm_precision: null handle");
+    FI_REQUIRE(precision == FI_FARMER_LSTM_FP32 || precision == FI_FARMER_LSTM_BF16,
+               "farmer_set_lstm_precision: precision must be FI_FARMER_LSTM_FP32 (0) or FI_FARMER_LSTM_BF16 (1)");
+    if (f->used) return fail(FI_ERR_STATE, "farmer_set_lstm_precision: the handle has already stepped or run a forward");
+    const bool want = precision == FI_FARMER_LSTM_BF16;
+    if (want == f->lstm_bf16) return FI_OK;
+    const size_t BT = (size_t)f->B * f->T;
+    if (want && BT * G >= ((size_t)1 << 31))
+        return fail(FI_ERR_UNSUPPORTED, "farmer_set_lstm_precision: B*T*512 must stay < 2^31; the handle stays in fp32");
+    FI_HIP_CHECK(hipSetDevice(f->dev));
+    FI_HIP_CHECK(hipStreamSynchronize(f->stream));
+    // the new mode's buffers first: when one does not fit, they go again and the handle is as it was
+    int rc = FI_OK;
+    auto A = [&](auto** p, size_t floats) {
+        float* q = nullptr;
+        if (rc == FI_OK) rc = falloc(f, &q, floats);
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+    };
+    auto drop = [&](bool bf16) {
+        if (bf16) ffree(f, &f->img), ffree(f, &f->gates16), ffree(f, &f->hprev16), ffree(f, &f->dG16), ffree(f, &f->slab16);
+        else ffree(f, &f->gates), ffree(f, &f->hprev), ffree(f, &f->dG);
+    };
+    if (want) {
+        f->splits16 = ops->splits((int)BT);
+        A(&f->img, kLstmImgElems / 2); A(&f->gates16, BT * G / 2); A(&f->hprev16, BT * H / 2); A(&f->dG16, BT * G / 2);
+        A(&f->slab16, ops->slab_floats(f->splits16));
+    } else {
+        A(&f->gates, BT * G); A(&f->hprev, BT * H); A(&f->dG, BT * G);
+    }
+    drop(rc == FI_OK ? !want : want);
+    FI_TRY(rc);
+    f->lstm_bf16 = want;
+    f->ops = ops;
+    FI_TRY(lstm_images(f));  // parameters set before the mode are taken too
+    FI_HIP_CHECK(hipStreamSynchronize(f->stream));
+    return FI_OK;
+}
+
+int fi::farmer::lstm_precision(const fi_farmer* f) {
+    FI_REQUIRE(f, "farmer_lstm_precision: null handle");
+    return f->lstm_bf16 ? FI_FARMER_LSTM_BF16 : FI_FARMER_LSTM_FP32;
 }
 
 extern "C" void* fi_farmer_stream(fi_farmer* f) { return f ? (void*)f->stream : nullptr; }

@@ -142,6 +142,17 @@ class FarmerLstmModel:
         p = np.ascontiguousarray(p, np.float32)
         _abi.check(lib().fi_farmer_set_params(self._h, p.ctypes.data, p.size), "fi_farmer_set_params")
 
+    def set_lstm_precision(self, precision) -> None:
+        """"bf16" | "fp32" (include/fi_farmer_lstm.h), before the first step or forward."""
+        from . import farmer_lstm
+        _abi.check(farmer_lstm.lib().fi_farmer_set_lstm_precision(self._h, farmer_lstm.precision(precision)),
+                   "fi_farmer_set_lstm_precision")
+
+    @property
+    def lstm_precision(self) -> str:
+        from . import farmer_lstm
+        return "bf16" if farmer_lstm.lib().fi_farmer_lstm_precision(self._h) == farmer_lstm.BF16 else "fp32"
+
     def get_params(self) -> np.ndarray:
         out = np.empty(param_count(), np.float32)
         _abi.check(lib().fi_farmer_get_params(self._h, out.ctypes.data, out.size), "fi_farmer_get_params")
