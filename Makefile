@@ -7,7 +7,7 @@ LIBDIR := freeimpala_amd/lib
 OBJDIR := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-result -Wno-unused-value \
             -munsafe-fp-atomics
-SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/vmpo.hip $(CSRC)/upgo.hip $(CSRC)/mlp_bf16.hip $(CSRC)/farmer_lstm_bf16.hip $(CSRC)/learner.cpp
+SRCS := $(CSRC)/farmer.hip $(CSRC)/vtrace.hip $(CSRC)/gemm_f32.hip $(CSRC)/misc.hip $(CSRC)/atari.hip $(CSRC)/atari_fr.hip $(CSRC)/fc_gemm.hip $(CSRC)/actor.hip $(CSRC)/rollout.hip $(CSRC)/gather.hip $(CSRC)/ring.hip $(CSRC)/prio.hip $(CSRC)/weights.hip $(CSRC)/env.hip $(CSRC)/breakout.hip $(CSRC)/publish.hip $(CSRC)/explore.hip $(CSRC)/diag.hip $(CSRC)/popart.hip $(CSRC)/surrogate.hip $(CSRC)/target.hip $(CSRC)/kl.hip $(CSRC)/vmpo.hip $(CSRC)/upgo.hip $(CSRC)/mlp_bf16.hip $(CSRC)/farmer_lstm_bf16.hip $(CSRC)/farmer_act.hip $(CSRC)/learner.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) $(wildcard include/fi_*.h)
 
